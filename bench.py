@@ -23,6 +23,11 @@ the prefill engine's cache (one kv_pull launch per hand-off message; GPU default
 packed send/recv (parallel/pd_driver.py); TTFT is measured on the decode side (includes
 the hand-off).
 
+A plain run (`--gpus 1 --steps K --warmup W`) builds the engine, runs W warm-up and K timed
+waves and prints the line; everything else is behind an option of its own.  --dump-outputs
+DIR: rank 0 also writes the two leading ids its last timed wave generated for every request
+(DIR/leading_token_ids.npy; dump_outputs says why those).
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -89,7 +94,47 @@ def parse():
                          "kernel table")
     ap.add_argument("--profile-steps", type=int, default=0,
                     help="extra untimed waves run after timing (for rocprofv3 captures)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed waves, rank 0 writes the two leading token ids its last "
+                         "timed wave generated for every request to DIR/leading_token_ids.npy "
+                         "(float64, submission order); prompts and weights are seeded, so the "
+                         "inputs are the same every run (not with --mode pd)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline figure (none today)")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+# ids kept per request: the prefill's argmax and the first decode step's
+DUMP_LEADING = 2
+
+
+def dump_outputs(path: str, rows: list) -> None:
+    """Write the leading generated ids of every request of one wave as
+    DIR/leading_token_ids.npy: float64 [requests, DUMP_LEADING], in submission order, -1 where
+    a request generated fewer.  Column 0 is the argmax of the request's prefill, column 1 the
+    output of its first decode step (decode GEMM chain, paged decode attention, sampler) on
+    that fixed context.  Past 64 MB a fixed, seeded sample of the requests (in order) is
+    written instead.
+
+    Why not every id: the dump is there to compare runs and builds, so it holds what is a
+    function of the seeded inputs.  From the third id on a row is not: the fused decode GEMM
+    epilogues sum the next RMSNorm's squares with fp32 atomics (csrc/kernels/dgemm.hip), in
+    whatever order the workgroups arrive, and random-init weights soon generate repeating ids
+    with near-flat logits, where that last-bit difference flips a greedy near-tie in about
+    1 % of the rows per step; the rest of such a row follows the flipped id.  Measured on
+    MI355X over 7 pairs of runs of one build: the two leading ids agreed in all 256 requests
+    of every pair, the earliest difference was in the third id, whole rows agreed in 49-68 of
+    256 (in all 256 with AKAP_FUSED_GEMM=0, at 2 % less throughput)."""
+    lead = [[float(x) for x in r[:DUMP_LEADING]] + [-1.0] * (DUMP_LEADING - len(r[:DUMP_LEADING]))
+            for r in rows]
+    keep = max(1, DUMP_LIMIT_BYTES // (8 * DUMP_LEADING))
+    if len(lead) > keep:
+        pick = np.sort(np.random.default_rng(0).choice(len(lead), size=keep, replace=False))
+        lead = [lead[i] for i in pick]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "leading_token_ids.npy"),
+            np.asarray(lead, dtype=np.float64).reshape(len(lead), DUMP_LEADING))
 
 
 def physical_devices(devs: list) -> int:
@@ -133,6 +178,10 @@ def self_launch(a) -> int | None:
 
 def main() -> int:
     a = parse()
+    if a.mode == "pd" and a.dump_outputs:
+        print("error: --dump-outputs: the P/D driver returns token counts, not ids",
+              file=sys.stderr)
+        return 2
     rc = self_launch(a)
     if rc is not None:
         return rc
@@ -246,6 +295,7 @@ def main() -> int:
         gaps = rng.exponential(1.0 / a.arrival_rate, size=a.num_requests)
         t_arr = time.time() + np.cumsum(gaps) - gaps[0]
         last, first, ttft, ntok, i = {}, {}, [], 0, 0
+        ids = [[] for _ in range(a.num_requests)]
         while i < a.num_requests or eng.has_unfinished():
             now = time.time()
             while i < a.num_requests and t_arr[i] <= now:
@@ -269,9 +319,11 @@ def main() -> int:
                 else:
                     lat["itl"].append(now - last[o.req_id])
                 last[o.req_id] = now
-                if o.finished and len(o.output_ids) > 1:
-                    lat["tpot"].append((now - first[o.req_id]) / (len(o.output_ids) - 1))
-        return ntok, ttft
+                if o.finished:
+                    ids[int(o.req_id[1:])] = list(o.output_ids)
+                    if len(o.output_ids) > 1:
+                        lat["tpot"].append((now - first[o.req_id]) / (len(o.output_ids) - 1))
+        return ntok, ttft, ids
 
     def wave():
         if a.arrival_rate > 0 and not pd:
@@ -283,15 +335,15 @@ def main() -> int:
                 chunked = a.pd_push == "chunked" or (a.pd_push == "auto" and (
                     pair.transport == "ipc" or dist.get_backend() != "gloo"))
                 pair.run_prefill(prompts, sp, chunked=chunked)
-                return 0, []
+                return 0, [], []
             r = pair.run_decode(sp, time.time())
-            return r["output_tokens"], r["ttft"]
+            return r["output_tokens"], r["ttft"], []
         # int32 rows: the engine hands each to the scheduler in one copy (no per-id conversion)
         prompts = rng.integers(10, vocab_hi, size=(a.num_requests, a.input_len), dtype=np.int32)
         outs = eng.generate(None, sp, prompt_ids=prompts)
         ntok = sum(len(o.output_ids) for o in outs)
         ttfts = [o.ttft for o in outs if o.ttft is not None]
-        return ntok, ttfts
+        return ntok, ttfts, [o.output_ids for o in outs]
 
     def barrier():
         if gpu:
@@ -308,11 +360,11 @@ def main() -> int:
         log(f"[bench] warmup wave {i} {time.time() - t:.2f}s")
     barrier()
     t0 = time.perf_counter()
-    total, ttfts = 0, []
+    total, ttfts, last_ids = 0, [], []
     for i in range(a.steps):
         if pd and i:
             barrier()  # P/D: every wave starts together on both sides (TTFT clock)
-        n, tt = wave()
+        n, tt, last_ids = wave()
         total += n
         ttfts += tt
     barrier()
@@ -320,6 +372,8 @@ def main() -> int:
     log(f"[bench] host timers (all waves): {eng.timers}  steps={eng.steps}")
     log("[bench] execute s / steps by kind: " + ", ".join(
         f"{k} {v[0]:.3f}/{v[1]}" for k, v in getattr(eng, "step_kinds", {}).items()))
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last_ids)
     for _ in range(a.profile_steps):
         wave()
     if a.torch_profile and rank == 0:

@@ -7,6 +7,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -43,11 +44,59 @@ def _run(args, nproc=1, env=None):
     return res
 
 
-def test_bench_mono_single_process():
-    res = _run(["--model", "tiny-qwen3"] + SMALL)
+def test_bench_mono_single_process(tmp_path):
+    args = ["--model", "tiny-qwen3"] + SMALL[:-4] + ["--steps", "2", "--warmup", "1"]
+    res = _run(args + ["--dump-outputs", str(tmp_path / "a")])
     # n_gpus counts physical devices (none on this CPU run); ranks counts processes
     assert res["n_gpus"] == 0 and res["ranks"] == 1 and res["config"]["parallelism"] == "dp1"
     assert res["scaling"] == "weak"
+    # --steps N times N waves: value is output tok/s over the timed window, ms_per_step that
+    # window over N, so their product gives back N * requests * output_len tokens
+    assert res["steps"] == 2
+    tokens = res["value"] * res["ms_per_step"] * res["steps"] / 1000
+    assert abs(tokens - 2 * 6 * 8) < 0.5
+    # --dump-outputs: the two leading ids the last timed wave generated for each request,
+    # float64; a second run with the same arguments (here also --full, which adds nothing to
+    # the line's keys) serves the same seeded prompts and writes the same ids
+    ids = np.load(tmp_path / "a" / "leading_token_ids.npy")
+    assert os.listdir(tmp_path / "a") == ["leading_token_ids.npy"]
+    assert ids.dtype == np.float64 and ids.shape == (6, 2)
+    assert (ids >= 0).all() and (ids == np.floor(ids)).all()
+    assert len(np.unique(ids, axis=0)) > 1, "every request generated the same ids"
+    again = _run(args + ["--full", "--dump-outputs", str(tmp_path / "b")])
+    assert set(again) == set(res)
+    assert np.array_equal(np.load(tmp_path / "b" / "leading_token_ids.npy"), ids)
+
+
+def test_bench_dump_outputs_refused_for_pd(tmp_path):
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--mode", "pd",
+                        "--dump-outputs", str(tmp_path), "--model", "tiny-qwen3"] + SMALL,
+                       capture_output=True, text=True, timeout=420, cwd="/tmp")
+    assert r.returncode == 2 and "--dump-outputs" in r.stderr
+    assert not os.listdir(tmp_path)
+
+
+def test_bench_dump_outputs_keeps_leading_ids_in_order(tmp_path, monkeypatch):
+    monkeypatch.syspath_prepend(REPO)
+    import bench
+
+    rows = [[10 + i, 20 + i, 30 + i] for i in range(9)] + [[19], []]
+    bench.dump_outputs(str(tmp_path), rows)
+    assert np.load(tmp_path / "leading_token_ids.npy").tolist() == \
+        [[10 + i, 20 + i] for i in range(9)] + [[19, -1], [-1, -1]]
+
+
+def test_bench_dump_outputs_samples_rows_past_the_size_limit(tmp_path, monkeypatch):
+    monkeypatch.syspath_prepend(REPO)
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 8 * 2 * 3)  # room for 3 rows
+    rows = [[10 + i, 20 + i, 30 + i] for i in range(9)]
+    bench.dump_outputs(str(tmp_path), rows)
+    a = np.load(tmp_path / "leading_token_ids.npy")
+    bench.dump_outputs(str(tmp_path), rows)
+    assert a.shape == (3, 2) and np.array_equal(a, np.load(tmp_path / "leading_token_ids.npy"))
+    assert all(r in [x[:2] for x in rows] for r in a.tolist()) and (np.diff(a[:, 0]) > 0).all()
 
 
 def test_bench_data_parallel_two_ranks():

@@ -3,6 +3,8 @@ ansible/kubectl/kind are not installed here, so the CLI runs against a recording
 `ansible-playbook`, playbooks/manifests are checked structurally, and the exporter reads
 a synthetic amdgpu sysfs tree."""
 import glob
+import hashlib
+import json
 import os
 import stat
 import subprocess
@@ -519,20 +521,21 @@ def test_rocprof_bridge(tmp_path):
     assert "akap_kernel_calls_total" in txt and " 10" in txt
 
 
-REF_TEMPLATES = "/root/reference/templates"
+REF_TEMPLATE_DIGESTS = os.path.join(ROOT, "tests", "golden",
+                                    "reference_chat_template_digests.json")
 
 
 @pytest.mark.parametrize("name", ["phi", "opt"])
 def test_chat_template_configmaps_byte_identical_to_reference(name):
     """the phi/opt ConfigMaps we generate are byte-identical to the
-    reference's templates/<name>-chat-template.yaml (parity pinned against the reference's
-    own files when they are present; skipped where the reference is not mounted)."""
-    path = os.path.join(REF_TEMPLATES, f"{name}-chat-template.yaml")
-    if not os.path.exists(path):
-        pytest.skip("reference templates not mounted here")
-    ref = open(path).read()
-    assert chat_template.configmap_text(name) == ref
-    assert yaml.safe_load(ref)["data"]["template.jinja"] == chat_template.BUILTIN[name]
+    reference's templates/<name>-chat-template.yaml: same length and SHA-256 as recorded
+    from the reference's own files in tests/golden/."""
+    with open(REF_TEMPLATE_DIGESTS) as f:
+        ref = json.load(f)[name]
+    text = chat_template.configmap_text(name).encode()
+    assert len(text) == ref["bytes"]
+    assert hashlib.sha256(text).hexdigest() == ref["sha256"]
+    assert yaml.safe_load(text)["data"]["template.jinja"] == chat_template.BUILTIN[name]
 
 
 def test_reference_template_rendering_quirks_pinned():

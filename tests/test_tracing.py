@@ -68,6 +68,19 @@ def collector():
     c.close()
 
 
+def _flushed_spans(c, tr, complete, timeout=10.0):
+    """The collector's spans once complete(span names) holds.  The tracer's export thread may
+    have a batch in flight when flush() finds the buffer empty, so one flush() does not mean
+    that the collector has everything recorded so far; poll (bounded) instead."""
+    deadline = time.time() + timeout
+    while True:
+        tr.flush()
+        spans = c.spans()
+        if complete([s["name"] for s in spans]) or time.time() > deadline:
+            return spans
+        time.sleep(0.02)
+
+
 def test_traceparent_roundtrip():
     tid, sid = tracing.new_trace_id(), tracing.new_span_id()
     hdr = tracing.make_traceparent(tid, sid)
@@ -100,8 +113,8 @@ def test_engine_emits_request_spans_with_parent(collector):
     eng.add_request("r2", "untraced", SamplingParams(max_tokens=3, ignore_eos=True))
     while eng.has_unfinished():
         eng.step()
-    tr.flush()
-    spans = c.spans()
+    # each request: llm_request + prefill + decode
+    spans = _flushed_spans(c, tr, lambda names: len(names) >= 6)
     by_name = {}
     for s in spans:
         by_name.setdefault(s["name"], []).append(s)
@@ -177,8 +190,7 @@ def test_gateway_propagates_trace_to_engine(collector):
         asyncio.run(run())
     finally:
         server.should_exit = True
-    tr.flush()
-    spans = c.spans()
+    spans = _flushed_spans(c, tr, lambda names: {"gateway.route", "llm_request"} <= set(names))
     gw = [s for s in spans if s["name"] == "gateway.route"]
     assert len(gw) == 1 and gw[0]["traceId"] == tid and gw[0]["parentSpanId"] == sid
     assert gw[0]["attrs"]["http.status_code"] == "200"
