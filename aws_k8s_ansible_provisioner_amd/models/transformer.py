@@ -448,22 +448,12 @@ class DecoderLM:
         Tensor parallel: the row-parallel O / down projections store their partial sums and
         the residual epilogue moves into the all-reduce (comm.tp_all_reduce_resnorm: the
         custom xGMI kernel applies it in its store pass), so a TP layer is still 4 GEMM
-        launches + 2 all-reduce launches + attention.  Plan from gemm_tuner.tune_fused:
-        projection -> (split-K, prefetch depth, LDS-DMA tile width[, ring, in-launch])."""
-        from ..ops import gemm_tuner
-
+        launches + 2 all-reduce launches + attention.  Plan from gemm_tuner.fused_plan:
+        projection -> the ops.gemm_variant.Variant its GEMM runs (or that record's fields as
+        a sequence, trailing ones defaulted)."""
         T = input_ids.shape[0]
         eps = self.cfg.rms_eps
         L = len(self.layers)
-
-        def cfg_(name):  # plan entry (split-K, prefetch, tile width[, ring, in-launch combine,
-            #                            kgemm rows])
-            e = tuple(plan[name])
-            s_, p_ = e[:2]
-            b_, n_, i_, k_, m_ = gemm_tuner.variant_fields(e[2:])[:5]
-            return dict(splitk=s_, pf=p_, bn=b_, ns=n_, inlaunch=bool(i_), km=k_, bm=m_)
-
-        c_qkv, c_o, c_gu, c_d = (cfg_(n) for n in ("w_qkv", "w_o", "w_gate_up", "w_down"))
         tp = self.ps.tp_size
         if tp == 1:
             # one launch (ops.embedding_prep): the embedding rows, the first layer's
@@ -482,7 +472,7 @@ class DecoderLM:
             ss_in = None
         for li, lw in enumerate(self.layers):
             nxt = self.layers[li + 1].w_qkv if li + 1 < L else None
-            qkv = ops.dgemm(a1, lw.w_qkv, eps=eps, ss_in=ss_in, **c_qkv)
+            qkv = ops.dgemm(a1, lw.w_qkv, eps=eps, ss_in=ss_in, variant=plan["w_qkv"])
             attn = torch.empty(T, self.hq, self.D, dtype=self.dtype, device=self.device)
             if PREFETCH_WEIGHTS:  # A/B knob: warm the layer's remaining weights in MALL
                 ops.l2_prefetch([lw.w_o, lw.w_gate_up, lw.w_down, nxt])
@@ -495,27 +485,28 @@ class DecoderLM:
                 tail_slot=batch.tail_slot)
             a2 = torch.empty_like(residual)
             if tp > 1:
-                part = ops.dgemm(attn.view(T, self.hq * self.D), lw.w_o, eps=eps, **c_o)
+                part = ops.dgemm(attn.view(T, self.hq * self.D), lw.w_o, eps=eps,
+                                 variant=plan["w_o"])
                 comm.tp_all_reduce_resnorm(part, residual, lw.ln2, a2, ss[2 * li])
             else:
                 ops.dgemm(attn.view(T, self.hq * self.D), lw.w_o, eps=eps, out=residual,
                           epi=ops.EPI_RESNORM, ss_out=ss[2 * li], a_out=a2, ln_out=lw.ln2,
-                          **c_o)
+                          variant=plan["w_o"])
             act = ops.dgemm(a2, lw.w_gate_up, eps=eps, ss_in=ss[2 * li], epi=ops.EPI_SILU,
-                            **c_gu)
+                            variant=plan["w_gate_up"])
             if li + 1 < L:
                 a1 = torch.empty_like(residual)
                 if tp > 1:
-                    part = ops.dgemm(act, lw.w_down, eps=eps, **c_d)
+                    part = ops.dgemm(act, lw.w_down, eps=eps, variant=plan["w_down"])
                     comm.tp_all_reduce_resnorm(part, residual, self.layers[li + 1].ln1, a1,
                                                ss[2 * li + 1])
                 else:
                     ops.dgemm(act, lw.w_down, eps=eps, out=residual, epi=ops.EPI_RESNORM,
                               ss_out=ss[2 * li + 1], a_out=a1, ln_out=self.layers[li + 1].ln1,
-                              **c_d)
+                              variant=plan["w_down"])
                 ss_in = ss[2 * li + 1]
             else:
-                x = comm.tp_all_reduce(ops.dgemm(act, lw.w_down, eps=eps, **c_d))
+                x = comm.tp_all_reduce(ops.dgemm(act, lw.w_down, eps=eps, variant=plan["w_down"]))
         h, _ = ops.fused_add_rms_norm(x, residual, self.final_norm, eps)
         return h
 

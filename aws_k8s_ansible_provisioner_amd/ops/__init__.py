@@ -18,6 +18,7 @@ from typing import Optional
 import torch
 
 from . import reference as ref
+from .gemm_variant import Variant
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _LIB = os.path.join(_PKG, "_C.so")
@@ -326,9 +327,7 @@ def linear(x: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = None)
             return wgemm(x, w, out=out)
         if choice is not None:  # measured at engine start (cold weights, real layers)
             if choice[0] == "dgemm" and x.stride(-1) == 1:
-                bn, ns, inl, km, bm = gemm_tuner.variant_fields(choice[3:])[:5]
-                return dgemm(x, w, PRO_PLAIN, choice[1], choice[2], out=out, bn=bn, ns=ns,
-                             inlaunch=inl, km=km, bm=bm)
+                return dgemm(x, w, out=out, variant=choice[1])
             split = choice[1] if choice[0] == "hip" else 0
     if split is None:
         use_hip = (x.is_cuda and _GEMM_MODE != "torch" and x.dim() == 2 and x.stride(-1) == 1
@@ -347,12 +346,8 @@ def linear(x: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = None)
     if out is None:
         out = torch.empty(M, N, dtype=x.dtype, device=x.device)
     s = split or gemm_splitk(M, N, K)
-    if s > 1:
-        ws = torch.empty(s * M * N, dtype=torch.float32, device=x.device)
-    else:
-        ws = _EMPTY_F32.get(x.device)
-        if ws is None:
-            ws = _EMPTY_F32[x.device] = torch.empty(1, dtype=torch.float32, device=x.device)
+    ws = (torch.empty(s * M * N, dtype=torch.float32, device=x.device) if s > 1 else
+          _empty_f32(x.device))
     torch.ops.akap.gemm(out, x, w, ws, s)
     return out
 
@@ -389,7 +384,7 @@ def dgemm(x: torch.Tensor, w: torch.Tensor, pro: int = PRO_PLAIN, splitk: int = 
           ss_in: Optional[torch.Tensor] = None, ss_out: Optional[torch.Tensor] = None,
           a_out: Optional[torch.Tensor] = None, ln_out: Optional[torch.Tensor] = None,
           bn: int = 0, ns: int = 0, inlaunch: bool = False, km: int = 0,
-          bm: int = 64) -> torch.Tensor:
+          bm: int = 64, variant=None) -> torch.Tensor:
     """Fused decode GEMM (csrc/kernels/dgemm.hip): y = A @ w.T where A is produced from x by
     the prologue inside the GEMM's operand staging --
       PRO_PLAIN    A = x; with ss_in, rows of y are scaled by rsqrt(ss_in / K + eps)
@@ -418,7 +413,9 @@ def dgemm(x: torch.Tensor, w: torch.Tensor, pro: int = PRO_PLAIN, splitk: int = 
     serving step -- so the tuner never emits it and gemm_tuner.load_cache refuses plans
     naming it.
     km = 16 | 32 selects csrc/kernels/kgemm.hip instead: km x 32 output tiles with the K split
-    over the workgroup's waves (plain prologue, store / residual epilogues, no split-K)."""
+    over the workgroup's waves (plain prologue, store / residual epilogues, no split-K).
+    variant: a gemm_variant.Variant (or its fields as a sequence) in place of those keywords."""
+    v = Variant(splitk, pf, bn, ns, inlaunch, km, bm) if variant is None else Variant.of(variant)
     M = x.shape[0]
     N, K = w.shape
     if out is None:
@@ -445,24 +442,32 @@ def dgemm(x: torch.Tensor, w: torch.Tensor, pro: int = PRO_PLAIN, splitk: int = 
         else:
             out.copy_(y.to(out.dtype))
         return out
-    if km:
-        torch.ops.akap.kgemm(out, x, w, km, epi, eps, ss_in, ss_out, a_out, ln_out)
+    if v.family == "kgemm":
+        torch.ops.akap.kgemm(out, x, w, v.km, epi, eps, ss_in, ss_out, a_out, ln_out)
         return out
-    counters = None
-    if splitk > 1:
-        inl = inlaunch and (bn or (pro == PRO_PLAIN and splitk in (2, 4, 8)))
-        n = (gdgemm_ws_floats(M, N, splitk, bn or 64, bm if bn else 64) if (bn or inl) else
-             splitk * M * N + (splitk * M if pro == PRO_ADDNORM else 0))
-        ws = torch.empty(n, dtype=torch.float32, device=x.device)
-        if inl or bn == 256:  # bn 256: the combine is always in the launch
-            counters = gemm_counters(x.device)
-    else:
-        ws = _EMPTY_F32.get(x.device)
-        if ws is None:
-            ws = _EMPTY_F32[x.device] = torch.empty(1, dtype=torch.float32, device=x.device)
-    torch.ops.akap.dgemm(out, x, w, ws, pro, splitk, pf, residual, residual_out, ln, eps, epi,
-                         ss_in, ss_out, a_out, ln_out, bn, ns, counters, bm)
+    ws, counters = dgemm_workspace(M, N, v, pro, x.device)
+    torch.ops.akap.dgemm(out, x, w, ws, pro, v.splitk, v.pf, residual, residual_out, ln, eps, epi,
+                         ss_in, ss_out, a_out, ln_out, v.bn, v.ns, counters, v.bm)
     return out
+
+
+def _combines_in_launch(splitk: int, bn: int, inlaunch: bool, pro: int = PRO_PLAIN) -> bool:
+    """Whether a dgemm launch asked for inlaunch combines its K slices itself: every LDS-DMA
+    variant can; the register ring only with the plain prologue and 2 | 4 | 8 slices."""
+    return bool(inlaunch and splitk > 1 and (bn or (pro == PRO_PLAIN and splitk in (2, 4, 8))))
+
+
+def dgemm_workspace(M: int, N: int, v: Variant, pro: int, device):
+    """(fp32 split-K workspace, tile tickets or None) one torch.ops.akap.dgemm launch of
+    variant v needs -- the only place that sizes them (ops.cpp refuses an undersized one)."""
+    if v.splitk == 1:
+        return _empty_f32(device), None
+    inl = _combines_in_launch(v.splitk, v.bn, v.inlaunch, pro)
+    n = (gdgemm_ws_floats(M, N, v.splitk, v.bn or 64, v.bm if v.bn else 64) if (v.bn or inl) else
+         v.splitk * M * N + (v.splitk * M if pro == PRO_ADDNORM else 0))
+    ws = torch.empty(n, dtype=torch.float32, device=device)
+    # tickets: the probe-only 256 x 256 body always combines in the launch
+    return ws, gemm_counters(device) if (inl or v.probe_only) else None
 
 
 def dgemm_supported(M: int, N: int, K: int, splitk: int, pf: int, epi: int = EPI_STORE,
@@ -476,8 +481,8 @@ def dgemm_supported(M: int, N: int, K: int, splitk: int, pf: int, epi: int = EPI
         return False
     if bm != 64 and not (bm == 128 and bn == 128) and not (bm == 256 and bn in (64, 128)):
         return False
-    inl = inlaunch and splitk > 1 and (bn or splitk in (2, 4, 8))
-    if inlaunch and splitk > 1 and not bn and splitk not in (2, 4, 8):
+    inl = _combines_in_launch(splitk, bn, inlaunch)
+    if inlaunch and splitk > 1 and not inl:
         return False  # the register-ring combine has 2 | 4 | 8 slices
     if epi == EPI_SILU and ((splitk != 1 and not inl) or N % 32):
         return False
@@ -546,6 +551,14 @@ def gemm_ctr_error(device, clear: bool = True) -> int:
 
 
 _EMPTY_F32: dict = {}
+
+
+def _empty_f32(device) -> torch.Tensor:
+    """The one-float workspace of a launch without split-K (one per device)."""
+    ws = _EMPTY_F32.get(device)
+    if ws is None:
+        ws = _EMPTY_F32[device] = torch.empty(1, dtype=torch.float32, device=device)
+    return ws
 
 
 def gemm_splitk(M: int, N: int, K: int) -> int:

@@ -23,19 +23,18 @@ from typing import Optional, Sequence
 
 import torch
 
-Choice = tuple  # ("torch",) | ("hip", splitk) | ("dgemm", splitk, prefetch_depth[, lds_dma_bn,
-#                 ring_slots, in_launch_combine]) | ("wgemm",)
+from .gemm_variant import Variant
+
+Choice = tuple  # ("torch",) | ("wgemm",) | ("hip", splitk) | ("dgemm", Variant)
 _PLAN: dict = {}
 
-# positional defaults of a "dgemm" choice's variant fields after (split-K, prefetch):
-# (LDS-DMA tile width, ring depth, in-launch combine, kgemm rows, tile rows)
-VARIANT_DEFAULTS = (0, 0, False, 0, 64)
 
-
-def variant_fields(v) -> tuple:
-    """(bn, ns, inlaunch, km, bm) of a choice's tail, missing trailing fields defaulted."""
-    v = tuple(v)
-    return v + VARIANT_DEFAULTS[len(v):]
+def _choice(c) -> Choice:
+    """A plan value with its dgemm variant as a Variant: cache files and hand-written plans
+    spell it flat, ("dgemm", splitk, pf, ...)."""
+    c = tuple(c)
+    flat = c[0] == "dgemm" and not isinstance(c[1], Variant)
+    return ("dgemm", Variant.of(c[1:])) if flat else c
 
 
 def plan() -> dict:
@@ -50,7 +49,8 @@ def reset() -> None:
 
 
 def lookup(M: int, N: int, K: int) -> Optional[Choice]:
-    return _PLAN.get((M, N, K))
+    c = _PLAN.get((M, N, K))
+    return None if c is None else _choice(c)
 
 
 def _timed(fn, n: int) -> float:
@@ -115,21 +115,6 @@ def _gd_variants(s: int, bns, M: int = 0):
                 yield bn, 3, inl, 256
 
 
-def _gd_call(M, N, K, s, bn, ns, inl, out, x, weights, epi, ss_in, ss_out, a_out, ln_out,
-             bm=64):
-    """fn(i) launching one gdgemm variant on weights[i % len] (workspace/tickets bound)."""
-    from . import gdgemm_ws_floats, gemm_counters
-
-    dev = x.device
-    ws = torch.empty(max(1, gdgemm_ws_floats(M, N, s, bn, bm) if s > 1 else 1), device=dev,
-                     dtype=torch.float32)
-    cnt = gemm_counters(dev) if (inl and s > 1) else None
-    n = len(weights)
-    return lambda i: torch.ops.akap.dgemm(out, x, weights[i % n], ws, 0, s, 1, None, None, None,
-                                          1e-6, epi, ss_in, ss_out, a_out, ln_out, bn, ns, cnt,
-                                          bm)
-
-
 def _rr_inl_ok(s: int) -> bool:
     """Time the register-ring in-launch combine at split s (AKAP_DGEMM_RR_INL=0: never, the
     round-5 candidate set, for A/Bs)."""
@@ -138,15 +123,40 @@ def _rr_inl_ok(s: int) -> bool:
     return s in (2, 4, 8) and os.environ.get("AKAP_DGEMM_RR_INL", "1") != "0"
 
 
-def _rr_inl_call(M, N, s, pf, out, x, weights, epi, ss_in, ss_out, a_out, ln_out):
-    """fn(i): the register-ring dgemm with its s K slices combined inside the launch."""
-    from . import gdgemm_ws_floats, gemm_counters
+def variants(M, N, K, epi=0, splits=(1, 2, 4, 8, 16), pfs=(2, 4, 8), bns=(64, 128),
+             kms=(16, 32), lm_head=False) -> list:
+    """Every Variant the tuners time for x[M, K] @ w[N, K].T with epilogue epi, in timing
+    order: per split-K the register ring at each prefetch depth, each followed by its
+    in-launch twin; then the LDS-DMA staged variants (csrc/kernels/gdgemm.hip; lm_head: only
+    their 256-row tiles, the narrow ones re-stream the activations once per 64-128 of ~150k
+    columns); after every split, kgemm (K split inside the workgroup, csrc/kernels/kgemm.hip)."""
+    def every():
+        for s in splits:
+            for pf in pfs:
+                for inl in ((False, True) if _rr_inl_ok(s) else (False,)):
+                    yield Variant(s, pf, inlaunch=inl)
+            for bn, ns, inl, bm in _gd_variants(s, bns, M):
+                if not lm_head or bm == 256:
+                    yield Variant(s, 1, bn, ns, inl, 0, bm)
+        for km in kms:
+            yield Variant(km=km)
 
-    ws = torch.empty(gdgemm_ws_floats(M, N, s, 64, 64), device=x.device, dtype=torch.float32)
-    cnt = gemm_counters(x.device)
-    n = len(weights)
-    return lambda i: torch.ops.akap.dgemm(out, x, weights[i % n], ws, 0, s, pf, None, None, None,
-                                          1e-6, epi, ss_in, ss_out, a_out, ln_out, 0, 0, cnt, 64)
+    return [v for v in every() if v.supported(M, N, K, epi)]
+
+
+def launcher(variant: Variant, M, out, x, weights, epi=0, ss_in=None, ss_out=None, a_out=None,
+             ln_out=None):
+    """fn(i) launching the variant on weights[i % len], its workspace and tickets bound."""
+    from . import PRO_PLAIN, dgemm_workspace
+
+    v, n = variant, len(weights)
+    if v.family == "kgemm":
+        return lambda i: torch.ops.akap.kgemm(out, x, weights[i % n], v.km, epi, 1e-6, ss_in,
+                                              ss_out, a_out, ln_out)
+    ws, cnt = dgemm_workspace(M, weights[0].shape[0], v, PRO_PLAIN, x.device)
+    return lambda i: torch.ops.akap.dgemm(out, x, weights[i % n], ws, PRO_PLAIN, v.splitk, v.pf,
+                                          None, None, None, 1e-6, epi, ss_in, ss_out, a_out,
+                                          ln_out, v.bn, v.ns, cnt, v.bm)
 
 
 def _rot(weights: Sequence[torch.Tensor], cold_bytes: int = 768 << 20) -> list:
@@ -164,54 +174,37 @@ def _rot(weights: Sequence[torch.Tensor], cold_bytes: int = 768 << 20) -> list:
 _RANK: dict = {}
 
 
+def _choice_launcher(c: Choice, M, y, x, weights):
+    """fn(i) computing y = x[M, K] @ weights[i % len].T the way plan value c says."""
+    n = len(weights)
+    if c[0] == "dgemm":
+        return launcher(c[1], M, y, x, weights)
+    if c[0] == "wgemm":
+        return lambda i: torch.ops.akap.wgemm(y, x, weights[i % n])
+    if c[0] == "hip":
+        ws = torch.empty(max(1, c[1] * M * y.shape[1]), device=x.device, dtype=torch.float32)
+        return lambda i: torch.ops.akap.gemm(y, x, weights[i % n], ws, c[1])
+    return lambda i: torch.nn.functional.linear(x, weights[i % n])
+
+
 def _plain_candidates(M, weights, x, y, splits, pfs, bns, kms, lm_head):
     """(choice, fn) for every hand-written way to compute x[M, K] @ w.T (hipBLASLt apart)."""
-    from . import dgemm_supported, kgemm_supported
-
-    w0 = weights[0]
-    N, K = w0.shape
-    dev = w0.device
-    n = len(weights)
-    if K % 64 == 0:  # wide-row weight-streaming kernel (csrc/kernels/wgemm.hip)
-        yield ("wgemm",), (lambda i: torch.ops.akap.wgemm(y, x, weights[i % n]))
-    for s in (() if lm_head else splits):
-        if K // s < 256 or K % (64 * s):
-            continue
-        ws = torch.empty(max(1, s * M * N), device=dev, dtype=torch.float32)
-        yield ("hip", s), (lambda i, ws=ws, s=s: torch.ops.akap.gemm(y, x, weights[i % n], ws, s))
-    for s in splits:
-        for pf in pfs:
-            if not dgemm_supported(M, N, K, s, pf) or (s > 1 and K // s < 256):
-                continue
-            ws = torch.empty(max(1, s * M * N), device=dev, dtype=torch.float32)
-            yield ("dgemm", s, pf), (lambda i, ws=ws, s=s, pf=pf: torch.ops.akap.dgemm(
-                y, x, weights[i % n], ws, 0, s, pf))
-            if _rr_inl_ok(s):  # the same with the slices combined inside the launch
-                yield (("dgemm", s, pf, 0, 0, True),
-                       _rr_inl_call(M, N, s, pf, y, x, weights, 0, None, None, None, None))
-        for bn, ns, inl, bm in _gd_variants(s, bns, M):  # LDS-DMA staged variants (gdgemm.hip)
-            if (not dgemm_supported(M, N, K, s, 1, bn=bn, inlaunch=inl, bm=bm)
-                    or (s > 1 and K // s < 256) or (lm_head and bm != 256)):
-                continue
-            yield (("dgemm", s, 1, bn, ns, inl, 0, bm),
-                   _gd_call(M, N, K, s, bn, ns, inl, y, x, weights, 0, None, None, None, None,
-                            bm))
-    for km in kms:  # K split inside the workgroup (csrc/kernels/kgemm.hip)
-        if not kgemm_supported(M, N, K, km):
-            continue
-        yield (("dgemm", 1, 1, 0, 0, False, km),
-               lambda i, km=km: torch.ops.akap.kgemm(y, x, weights[i % n], km, 0, 1e-6, None,
-                                                     None, None, None))
+    N, K = weights[0].shape
+    # the wide-row weight-streaming kernel (csrc/kernels/wgemm.hip), the MFMA GEMM per split-K
+    choices = [("wgemm",)] * (K % 64 == 0) + [
+        ("hip", s) for s in (() if lm_head else splits) if K // s >= 256 and K % (64 * s) == 0]
+    choices += [("dgemm", v) for v in variants(M, N, K, 0, splits, pfs, bns, kms, lm_head)]
+    for c in choices:
+        yield c, _choice_launcher(c, M, y, x, weights)
 
 
 def tune(M: int, weights: Sequence[torch.Tensor], splits=(1, 2, 4, 8, 16),
          margin: float = 0.03, pfs=(2, 4, 8), bns=(64, 128), kms=(16, 32),
          lm_head: bool = False, allowed: Optional[set] = None) -> Choice:
     """Pick the fastest way to compute x[M, K] @ w.T for these same-shape weights.
-    hipBLASLt is kept unless the MFMA kernel is more than `margin` faster.  lm_head: only the
-    256-row LDS-DMA tiles among the gdgemm variants (the narrow ones re-stream the
-    activations once per 64-128 of ~150k columns).  allowed: time only these choices (the
-    shape-class pruning of tune_model); the ranking lands in _RANK[(M, N, K)]."""
+    hipBLASLt is kept unless the MFMA kernel is more than `margin` faster.  lm_head: see
+    variants().  allowed: time only these choices (the shape-class pruning of tune_model);
+    the ranking lands in _RANK[(M, N, K)]."""
     from . import gemm_counters  # noqa: F401  (ensures the native library is loaded)
 
     weights = _rot(weights)
@@ -221,7 +214,7 @@ def tune(M: int, weights: Sequence[torch.Tensor], splits=(1, 2, 4, 8, 16),
     x = torch.randn(M, K, device=dev, dtype=w0.dtype) * 0.1
     y = torch.empty(M, N, device=dev, dtype=w0.dtype)
     n = len(weights)
-    t_torch = _timed(lambda i: torch.nn.functional.linear(x, weights[i % n]), n)
+    t_torch = _timed(_choice_launcher(("torch",), M, y, x, weights), n)
     timed = [(t_torch, ("torch",))]
     for choice, fn in _plain_candidates(M, weights, x, y, splits, pfs, bns, kms, lm_head):
         if allowed is not None and choice not in allowed:
@@ -230,7 +223,7 @@ def tune(M: int, weights: Sequence[torch.Tensor], splits=(1, 2, 4, 8, 16),
     timed.sort(key=lambda tc: tc[0])
     _RANK[(M, N, K)] = [c for _, c in timed]
     t_best, best = timed[0]
-    if best[0] != "torch" and t_best > t_torch * (1.0 - margin):
+    if best != ("torch",) and t_best > t_torch * (1.0 - margin):
         best = ("torch",)
     _PLAN[(M, N, K)] = best
     return best
@@ -269,15 +262,11 @@ def _neighbour_allowed(M: int, anchors: list, rank_of) -> Optional[set]:
     return allowed
 
 
-def _gd_name(v) -> str:
-    bn, ns, inl, km, bm = variant_fields(v)[:5]
-    if km:
-        return f"k{km}"
-    if not bn:  # register ring (prefetch depth printed by the caller)
-        return "i" if inl else ""
-    if bm in (128, 256):
-        return f"g{bn}x{bm}" + ("i" if inl else "")
-    return f"g{bn}" + ("d" if ns >= 6 else "") + ("i" if inl else "")
+def _label(c: Choice) -> str:
+    """Log token of a plan value: "wgemm", "hip s4", "dgemm s2p4i"."""
+    if c[0] == "dgemm":
+        return f"dgemm s{c[1].splitk}{c[1].name}"
+    return c[0] + (f" s{c[1]}" if len(c) > 1 else "")
 
 
 def tune_model(model, Ms: Sequence[int], log=print) -> dict:
@@ -309,11 +298,7 @@ def tune_model(model, Ms: Sequence[int], log=print) -> dict:
     wins = {k: v for k, v in summary.items() if v[0] != "torch"}
     log(f"[gemm-tuner] {len(summary)} decode GEMM shapes, HIP kernel chosen for "
         f"{len(wins)}: " + ", ".join(
-            f"M={m} {n} {c[0]}" + (f" s{c[1]}" if len(c) > 1 else "") +
-            (f"p{c[2]}" if len(c) == 3 or (len(c) > 3 and not c[3] and
-                                          not variant_fields(c[3:])[3]) else "") +
-            (_gd_name(c[3:]) if len(c) > 3 else "")
-            for (m, n), c in sorted(wins.items())))
+            f"M={m} {n} {_label(c)}" for (m, n), c in sorted(wins.items())))
     return summary
 
 
@@ -330,7 +315,19 @@ _FUSED_ROLES = (("w_qkv", 0), ("w_o", 1), ("w_gate_up", 2), ("w_down", 1))  # (w
 
 
 def fused_plan(M: int) -> Optional[dict]:
-    return _FUSED.get(M)
+    """Projection name -> Variant of the fused chain chosen at M rows (None: unfused)."""
+    pl = _FUSED.get(M)
+    return None if pl is None else {n: Variant.of(v) for n, v in pl.items()}
+
+
+def _fused_candidates(M, N, K, epi, splits, pfs, bns, kms) -> list:
+    """variants() in the order the chain tuner times them (equal times keep the first): per
+    split-K the register ring, then its in-launch twins, then the LDS-DMA variants, with
+    kgemm after split 1's."""
+    def order(v):
+        return v.splitk, {"ring": int(v.inlaunch), "lds": 2, "kgemm": 3}[v.family]
+
+    return sorted(variants(M, N, K, epi, splits, pfs, bns, kms), key=order)
 
 
 def _time_unfused(M: int, model) -> float:
@@ -351,9 +348,9 @@ def _time_unfused(M: int, model) -> float:
 
 def tune_fused(model, Ms: Sequence[int], log=print, splits=(1, 2, 4, 8), pfs=(2, 4, 8),
                verbose: Optional[bool] = None, bns=(64, 128), kms=(16, 32)) -> dict:
-    """Pick (split-K, prefetch) for each fused-chain GEMM at each M and keep the fused chain
+    """Pick the Variant of each fused-chain GEMM at each M and keep the fused chain
     for the M where it beats the unfused chain (both timed on the real cold layer weights)."""
-    from . import EPI_SILU, dgemm_supported, kgemm_supported
+    from . import EPI_SILU
 
     if not model.layers or any(getattr(l, "moe", None) is not None for l in model.layers):
         return {}
@@ -370,7 +367,7 @@ def tune_fused(model, Ms: Sequence[int], log=print, splits=(1, 2, 4, 8), pfs=(2,
     roles = _FUSED_ROLES if model.ps.tp_size == 1 else tuple(
         (n, 0 if n in ("w_o", "w_down") else e) for n, e in _FUSED_ROLES)
     anchors = anchor_ms(Ms)
-    franks: dict = {}  # (M, name) -> candidate tuples by time (anchors only)
+    franks: dict = {}  # (M, name) -> candidate variants by time (anchors only)
     order = anchors + [m for m in sorted(set(Ms)) if m not in anchors]
     for M in order:
         t_unfused = _time_unfused(M, model)
@@ -383,69 +380,34 @@ def tune_fused(model, Ms: Sequence[int], log=print, splits=(1, 2, 4, 8), pfs=(2,
             ws_ = _rot([getattr(l, name) for l in model.layers])
             L = len(ws_)
             N, K = ws_[0].shape
-            t_plain = _time_best_plain(M, name, ws_)
-            t_unfused += t_plain
             x = torch.randn(M, K, device=dev, dtype=dt) * 0.1
             out = (torch.randn(M, N, device=dev, dtype=dt) if epi == 1 else
                    torch.empty(M, N // 2 if epi == EPI_SILU else N, device=dev, dtype=dt))
             ss = torch.full((M,), float(K), device=dev, dtype=torch.float32)
             ss_o = torch.zeros(M, device=dev, dtype=torch.float32)
             a_o = torch.empty(M, N, device=dev, dtype=dt)
+            # the unfused chain runs the plan's choice for this projection (hipBLASLt unless tuned)
+            t_plain = _timed(_choice_launcher(lookup(M, N, K) or ("torch",), M, a_o, x, ws_), L)
+            t_unfused += t_plain
             ln = model.layers[0].ln2 if N == model.layers[0].ln2.numel() else None
-            best = None
             ss_in_, ss_out_ = (None if epi == 1 else ss), (ss_o if epi == 1 else None)
             a_o_, ln_ = (a_o if epi == 1 else None), (ln if epi == 1 else None)
-            for s in splits:
-                cands = [(pf, 0, 0, False, 0, 64) for pf in pfs] + \
-                    [(pf, 0, 0, True, 0, 64) for pf in pfs if _rr_inl_ok(s)] + \
-                    [(1, bn, ns, inl, 0, bm) for bn, ns, inl, bm in _gd_variants(s, bns, M)]
-                if s == 1:
-                    cands += [(1, 0, 0, False, km, 64) for km in kms
-                              if kgemm_supported(M, N, K, km, epi)]
-                for pf, bn, ns, inl, km, bm in cands:
-                    if allowed is not None and (s, pf, bn, ns, inl, km, bm) not in allowed:
-                        continue
-                    if km:
-                        fn = (lambda i, km=km: torch.ops.akap.kgemm(
-                            out, x, ws_[i % L], km, epi, 1e-6, ss_in_, ss_out_, a_o_, ln_))
-                        t = _timed(fn, L)
-                        timed_c.append((t, (s, pf, bn, ns, inl, km, bm)))
-                        if best is None or t < best[0]:
-                            best = (t, s, pf, bn, ns, inl, km, bm)
-                        continue
-                    if (not dgemm_supported(M, N, K, s, pf, epi, bn=bn, inlaunch=inl, bm=bm)
-                            or (s > 1 and K // s < 256)):
-                        continue
-                    if bn:
-                        fn = _gd_call(M, N, K, s, bn, ns, inl, out, x, ws_, epi, ss_in_,
-                                      ss_out_, a_o_, ln_, bm)
-                    elif inl:
-                        fn = _rr_inl_call(M, N, s, pf, out, x, ws_, epi, ss_in_, ss_out_, a_o_,
-                                          ln_)
-                    else:
-                        wsp = torch.empty(max(1, s * M * N), device=dev, dtype=torch.float32)
-                        fn = (lambda i, s=s, pf=pf, wsp=wsp: torch.ops.akap.dgemm(
-                            out, x, ws_[i % L], wsp, 0, s, pf, None, None, None, 1e-6, epi,
-                            ss_in_, ss_out_, a_o_, ln_, 0))
-                    t = _timed(fn, L)
-                    timed_c.append((t, (s, pf, bn, ns, inl, 0, bm)))
-                    if best is None or t < best[0]:
-                        best = (t, s, pf, bn, ns, inl, 0, bm)
-            franks[(M, name)] = [c for _, c in sorted(timed_c, key=lambda tc: tc[0])]
+            for v in _fused_candidates(M, N, K, epi, splits, pfs, bns, kms):
+                if allowed is None or v in allowed:
+                    fn = launcher(v, M, out, x, ws_, epi, ss_in_, ss_out_, a_o_, ln_)
+                    timed_c.append((_timed(fn, L), v))
+            timed_c.sort(key=lambda tv: tv[0])  # stable: equal times keep the timing order
+            franks[(M, name)] = [v for _, v in timed_c]
             if verbose:
                 log(f"[gemm-tuner] M={M} {name} top: " + ", ".join(
-                    f"{t:.2f}us s{c[0]}" + (_gd_name(c[2:]) if (c[2] or c[5]) else
-                                          f"p{c[1]}" + ("i" if c[4] else ""))
-                    for t, c in sorted(timed_c, key=lambda tc: tc[0])[:5]))
-            if best is None:
+                    f"{t:.2f}us s{v.splitk}{v.name}" for t, v in timed_c[:5]))
+            if not timed_c:
                 plan_m = None
                 break
-            plan_m[name] = best[1:]
-            t_fused += best[0]
-            detail.append(f"{name} {best[0]:.1f}/{t_plain:.1f} (s{best[1]}"
-                          + (_gd_name(best[3:]) if (best[3] or best[6]) else
-                             f"p{best[2]}" + ("i" if best[5] else ""))
-                          + ")")
+            t_win, plan_m[name] = timed_c[0]
+            t_fused += t_win
+            detail.append(f"{name} {t_win:.1f}/{t_plain:.1f} (s{plan_m[name].splitk}"
+                          f"{plan_m[name].name})")
         if plan_m is not None and t_fused < t_unfused:
             _FUSED[M] = plan_m
         chosen[M] = (t_fused, t_unfused, plan_m)
@@ -592,9 +554,14 @@ def save_cache(path: str, model, Ms: Sequence[int], prefill_m: int = 0) -> None:
     import json
     import os
 
+    def flat(c):  # on disk a dgemm choice is ["dgemm", *variant fields]
+        c = _choice(c)
+        return [c[0], *c[1]] if c[0] == "dgemm" else list(c)
+
     data = {"key": cache_key(model, Ms, prefill_m),
-            "plan": [[list(k), list(v)] for k, v in sorted(_PLAN.items())],
-            "fused": [[m, {n: list(t) for n, t in pl.items()}] for m, pl in sorted(_FUSED.items())],
+            "plan": [[list(k), flat(c)] for k, c in sorted(_PLAN.items())],
+            "fused": [[m, {n: list(Variant.of(v)) for n, v in pl.items()}]
+                      for m, pl in sorted(_FUSED.items())],
             "prefill": [[list(k), v] for k, v in sorted(_PREFILL.items())]}
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     tmp = f"{path}.tmp{os.getpid()}"
@@ -614,15 +581,11 @@ def load_cache(path: str, model, Ms: Sequence[int], prefill_m: int = 0) -> bool:
         return False
     if data.get("key") != cache_key(model, Ms, prefill_m):
         return False
-    plan_ = {tuple(k): tuple(v) for k, v in data["plan"]}
-    fused_ = {int(m): {n: tuple(t) for n, t in pl.items()} for m, pl in data["fused"]}
-    # the 256 x 256 stream-K body (bn = 256, pgemm_sk) is probe-only: a combine that times
-    # out there only sets GEMM_CTR_ERR, which no serving step reads -- never serve it from a
-    # (hand-edited or foreign) cache file
-    if any(c[0] == "dgemm" and len(c) > 3 and variant_fields(c[3:])[0] == 256
-           for c in plan_.values()) or any(
-            len(e) > 2 and variant_fields(e[2:])[0] == 256
-            for pl in fused_.values() for e in pl.values()):
+    plan_ = {tuple(k): _choice(c) for k, c in data["plan"]}
+    fused_ = {int(m): {n: Variant.of(v) for n, v in pl.items()} for m, pl in data["fused"]}
+    # never serve a probe-only variant from a (hand-edited or foreign) cache file
+    if any(c[0] == "dgemm" and c[1].probe_only for c in plan_.values()) or any(
+            v.probe_only for pl in fused_.values() for v in pl.values()):
         return False
     _PLAN.clear()
     _FUSED.clear()
@@ -632,37 +595,3 @@ def load_cache(path: str, model, Ms: Sequence[int], prefill_m: int = 0) -> bool:
     for k, v in data.get("prefill", []):
         _PREFILL[tuple(k)] = bool(v)
     return True
-
-
-def _time_best_plain(M: int, name: str, weights) -> float:
-    """us of the plan's choice for this projection (hipBLASLt unless tuned otherwise)."""
-    weights = _rot(weights)
-    w0 = weights[0]
-    N, K = w0.shape
-    x = torch.randn(M, K, device=w0.device, dtype=w0.dtype) * 0.1
-    c = _PLAN.get((M, N, K), ("torch",))
-    n = len(weights)
-    if c[0] == "dgemm":
-        y = torch.empty(M, N, device=w0.device, dtype=w0.dtype)
-        if len(c) > 6 and c[6]:
-            return _timed(lambda i: torch.ops.akap.kgemm(y, x, weights[i % n], c[6], 0, 1e-6, None,
-                                                         None, None, None), n)
-        if len(c) > 3 and c[3]:
-            bn, ns, inl, _, bm = variant_fields(c[3:])[:5]
-            return _timed(_gd_call(M, N, K, c[1], bn, ns, inl, y, x, weights, 0, None, None,
-                                   None, None, bm), n)
-        if len(c) > 5 and c[5]:
-            return _timed(_rr_inl_call(M, N, c[1], c[2], y, x, weights, 0, None, None, None,
-                                       None), n)
-        ws = torch.empty(max(1, c[1] * M * N), device=w0.device, dtype=torch.float32)
-        return _timed(lambda i: torch.ops.akap.dgemm(y, x, weights[i % n], ws, 0, c[1], c[2],
-                                                     None, None, None, 1e-6, 0, None, None,
-                                                     None, None, 0), n)
-    if c[0] == "wgemm":
-        y = torch.empty(M, N, device=w0.device, dtype=w0.dtype)
-        return _timed(lambda i: torch.ops.akap.wgemm(y, x, weights[i % n]), n)
-    if c[0] == "hip":
-        ws = torch.empty(max(1, c[1] * M * N), device=w0.device, dtype=torch.float32)
-        y = torch.empty(M, N, device=w0.device, dtype=w0.dtype)
-        return _timed(lambda i: torch.ops.akap.gemm(y, x, weights[i % n], ws, c[1]), n)
-    return _timed(lambda i: torch.nn.functional.linear(x, weights[i % n]), n)

@@ -37,27 +37,9 @@ for M in [int(v) for v in a.m.split(",")]:
         w64 = [w[:, :64].contiguous() for w in ws]
         x64 = x[:, :64].contiguous()
         rows.append(("floor(K=64,g64)", gt._timed(
-            gt._gd_call(M, N, 64, 1, 64, 0, False, y, x64, w64, 0, None, None, None, None), L)))
-        for s in (1, 2, 4, 8):
-            if K % (64 * s):
-                continue
-            for pf in (2, 4, 8):
-                if ops.dgemm_supported(M, N, K, s, pf):
-                    wsp = torch.empty(max(1, s * M * N), device="cuda", dtype=torch.float32)
-                    rows.append((f"s{s} reg p{pf}", gt._timed(
-                        lambda i, s=s, pf=pf, wsp=wsp: torch.ops.akap.dgemm(
-                            y, x, ws[i % L], wsp, 0, s, pf), L)))
-            for bn, ns, inl, bm in gt._gd_variants(s, (64, 128)):
-                if ops.dgemm_supported(M, N, K, s, 1, bn=bn, inlaunch=inl, bm=bm):
-                    rows.append((f"s{s} {gt._gd_name((bn, ns, inl, 0, bm))}", gt._timed(
-                        gt._gd_call(M, N, K, s, bn, ns, inl, y, x, ws, 0, None, None, None,
-                                    None, bm), L)))
-            if s == 1:
-                for km in (16, 32):
-                    if ops.kgemm_supported(M, N, K, km):
-                        rows.append((f"k{km}", gt._timed(
-                            lambda i, km=km: torch.ops.akap.kgemm(y, x, ws[i % L], km, 0, 1e-6,
-                                                                  None, None, None, None), L)))
+            gt.launcher(gt.Variant(bn=64), M, y, x64, w64), L)))
+        for v in gt.variants(M, N, K, splits=(1, 2, 4, 8)):  # the tuner's own candidates
+            rows.append((f"s{v.splitk}{v.name}", gt._timed(gt.launcher(v, M, y, x, ws), L)))
         rows.sort(key=lambda r: r[1])
         print(f"M={M:4d} {name:10s} N={N:6d} K={K:6d}: " + "  ".join(
             f"{n} {t:.1f}" for n, t in rows), flush=True)

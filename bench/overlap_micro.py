@@ -62,8 +62,7 @@ class Half:
 
     def pre(self, li):
         m, lw = self.m, self.m.layers[li]
-        s_, p_ = self.plan["w_qkv"][:2]
-        self.qkv = ops.dgemm(self.a1, lw.w_qkv, splitk=s_, pf=p_, eps=m.cfg.rms_eps,
+        self.qkv = ops.dgemm(self.a1, lw.w_qkv, variant=self.plan["w_qkv"], eps=m.cfg.rms_eps,
                              ss_in=self.ss_in)
 
     def attn(self, li):
@@ -77,22 +76,20 @@ class Half:
     def post(self, li):
         m, lw, eps, T = self.m, self.m.layers[li], self.m.cfg.rms_eps, self.T
         a2 = torch.empty_like(self.residual)
-        s_, p_ = self.plan["w_o"][:2]
-        ops.dgemm(self.at.view(T, m.hq * m.D), lw.w_o, splitk=s_, pf=p_, eps=eps,
+        ops.dgemm(self.at.view(T, m.hq * m.D), lw.w_o, variant=self.plan["w_o"], eps=eps,
                   out=self.residual, epi=ops.EPI_RESNORM, ss_out=self.ss[2 * li], a_out=a2,
                   ln_out=lw.ln2)
-        s_, p_ = self.plan["w_gate_up"][:2]
-        act = ops.dgemm(a2, lw.w_gate_up, splitk=s_, pf=p_, eps=eps, ss_in=self.ss[2 * li],
-                        epi=ops.EPI_SILU)
-        s_, p_ = self.plan["w_down"][:2]
+        act = ops.dgemm(a2, lw.w_gate_up, variant=self.plan["w_gate_up"], eps=eps,
+                        ss_in=self.ss[2 * li], epi=ops.EPI_SILU)
+        v_ = self.plan["w_down"]
         if li + 1 < len(m.layers):
             self.a1 = torch.empty_like(self.residual)
-            ops.dgemm(act, lw.w_down, splitk=s_, pf=p_, eps=eps, out=self.residual,
+            ops.dgemm(act, lw.w_down, variant=v_, eps=eps, out=self.residual,
                       epi=ops.EPI_RESNORM, ss_out=self.ss[2 * li + 1], a_out=self.a1,
                       ln_out=m.layers[li + 1].ln1)
             self.ss_in = self.ss[2 * li + 1]
         else:
-            x = ops.dgemm(act, lw.w_down, splitk=s_, pf=p_, eps=eps)
+            x = ops.dgemm(act, lw.w_down, variant=v_, eps=eps)
             self.h, _ = ops.fused_add_rms_norm(x, self.residual, m.final_norm, eps)
 
 

@@ -108,16 +108,17 @@ def test_fused_epilogues_gpu():
 def test_gemm_tune_cache_round_trip(tmp_path):
     """The persisted plan reloads only for the same model shapes / batch buckets / library."""
     from aws_k8s_ansible_provisioner_amd.ops import gemm_tuner
+    from aws_k8s_ansible_provisioner_amd.ops.gemm_variant import Variant
 
     m = DecoderLM(get_config("tiny-llama"), device="cpu", seed=0, max_model_len=64)
     Ms = [16, 32]
     w = m.layers[0].w_qkv
     gemm_tuner._PLAN.clear()
     gemm_tuner._FUSED.clear()
-    gemm_tuner._PLAN[(16,) + tuple(w.shape)] = ("dgemm", 1, 1, 128, 4, False, 0, 128)
+    gemm_tuner._PLAN[(16,) + tuple(w.shape)] = ("dgemm", Variant(1, 1, 128, 4, False, 0, 128))
     gemm_tuner._PLAN[(32,) + tuple(w.shape)] = ("wgemm",)
-    gemm_tuner._FUSED[32] = {"w_qkv": (1, 4, 0, 0, False, 0, 64),
-                             "w_o": (1, 1, 0, 0, False, 32, 64)}
+    gemm_tuner._FUSED[32] = {"w_qkv": Variant(1, 4, 0, 0, False, 0, 64),
+                             "w_o": Variant(1, 1, 0, 0, False, 32, 64)}
     want_plan, want_fused = dict(gemm_tuner._PLAN), dict(gemm_tuner._FUSED)
     path = str(tmp_path / "tune.json")
     gemm_tuner.save_cache(path, m, Ms)

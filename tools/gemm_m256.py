@@ -61,8 +61,7 @@ def main():
                                 continue
                             for ns in ((3, 6) if bm == 256 and bn == 128 else
                                        (3,) if bm == 256 else (4,)):
-                                fn = gt._gd_call(M, N, K, s, bn, ns, inl, y, x, ws_, 0, None,
-                                                 None, None, None, bm)
+                                fn = gt.launcher(gt.Variant(s, 1, bn, ns, inl, 0, bm), M, y, x, ws_)
                                 if bm == 256:
                                     y.fill_(float("nan"))
                                     fn(0)

@@ -34,8 +34,7 @@ def main():
     ws = [torch.randn(N, K, device="cuda", dtype=torch.bfloat16) * 0.02 for _ in range(L)]
     x = torch.randn(M, K, device="cuda", dtype=torch.bfloat16) * 0.5
     y = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
-    fn = gt._gd_call(M, N, K, a.split, a.bn, a.ns, False, y, x, ws, 0, None, None, None, None,
-                     a.bm)
+    fn = gt.launcher(gt.Variant(a.split, 1, a.bn, a.ns, bm=a.bm), M, y, x, ws)
     for i in range(a.iters):
         fn(i)
     torch.cuda.synchronize()

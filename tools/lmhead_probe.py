@@ -34,7 +34,7 @@ def main():
         res["wgemm"] = gt._timed(lambda i: torch.ops.akap.wgemm(y, x, wv[i % 3]), 3)
         if ops.dgemm_supported(M, V, K, 1, 1, bn=128, bm=256):
             res["g128x256"] = gt._timed(
-                gt._gd_call(M, V, K, 1, 128, 3, False, y, x, wv, 0, None, None, None, None, 256), 3)
+                gt.launcher(gt.Variant(1, 1, 128, 3, bm=256), M, y, x, wv), 3)
         res["pgemm(VP)"] = gt._timed(lambda i: torch.ops.akap.pgemm(yp, x, ws[i % 3], 0, None), 3)
         tok = torch.empty(M, dtype=torch.int64, device=dev)
 
