@@ -186,6 +186,28 @@ struct WGemmArgs {
 bool wgemm_supported(int M, int N, int K, int ldx, int ldw, int ldy);
 void launch_wgemm(const WGemmArgs& p, hipStream_t st);
 
+// ---- qgemm.hip: FP8-weight (e4m3fn bytes + per-channel fp32 scale) decode GEMM, M <= 256 ----
+//   Y[m,n] = bf16(scale[n] * sum_k X[m,k] * float(Wq[n,k])); no workspace, no cross-workgroup
+//   state: graph-capturable and bit-reproducible
+struct QGemmArgs {
+  const void* X;       // bf16 [M, K] (row stride ldx)
+  const void* Wq;      // uint8 [N, K] contiguous, OCP e4m3fn codes
+  const float* scale;  // [N]
+  void* Y;             // bf16 [M, N] (row stride ldy)
+  int M, N, K, ldx, ldy;
+};
+struct QGemmGeom {
+  int bm, bn;  // output tile of one 4-wave workgroup (K is split over its waves)
+  int grid;
+};
+// pure: the tile geometry launch_qgemm uses for a shape
+QGemmGeom qgemm_geometry(int M, int N, int K);
+bool qgemm_supported(int M, int N, int K, int ldx, int ldy);
+void launch_qgemm(const QGemmArgs& p, hipStream_t st);
+// out[n, k] = bf16(float(q[n, k]) * scale[n]); q uint8 [N, K], out bf16 [N, K], K % 16 == 0
+void launch_dequant_fp8(const void* q, const float* scale, void* out, long N, int K,
+                        hipStream_t st);
+
 // ---- sampling.hip ----
 struct SampleParams {
   const void* logits;  // [B, V] (row stride ld), fp32 or bf16

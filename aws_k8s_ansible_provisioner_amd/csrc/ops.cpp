@@ -492,6 +492,56 @@ void wgemm(Tensor out, Tensor x, Tensor w) {
   akap::launch_wgemm(a, cur_stream());
 }
 
+// FP8-weight decode GEMM (csrc/kernels/qgemm.hip): out[M, N] = bf16(scale[n] * x[M, K] @
+// float(wq[N, K])^T), wq = OCP e4m3fn bytes (uint8 or float8_e4m3fn), scale fp32 per channel.
+bool is_fp8_bytes(const Tensor& t) {
+  return t.scalar_type() == at::kByte || t.scalar_type() == at::kFloat8_e4m3fn;
+}
+
+void qgemm(Tensor out, Tensor x, Tensor wq, Tensor scale) {
+  CHECK_GPU(x); CHECK_GPU(wq); CHECK_GPU(scale); CHECK_GPU(out);
+  CHECK_BF16(x); CHECK_BF16(out);
+  TORCH_CHECK(is_fp8_bytes(wq), "qgemm: wq must be uint8 / float8_e4m3fn (e4m3fn codes)");
+  TORCH_CHECK(scale.scalar_type() == at::kFloat, "qgemm: scale must be fp32");
+  TORCH_CHECK(x.dim() == 2 && wq.dim() == 2 && out.dim() == 2 && scale.dim() == 1,
+              "qgemm: x, wq, out 2-D and scale 1-D");
+  CHECK_LAST_CONTIG(x); CHECK_LAST_CONTIG(out); CHECK_CONTIG(wq); CHECK_CONTIG(scale);
+  TORCH_CHECK(x.device() == wq.device() && x.device() == scale.device() &&
+              x.device() == out.device(), "qgemm: tensors on different devices");
+  const int M = x.size(0), N = wq.size(0), K = wq.size(1);
+  TORCH_CHECK(x.size(1) == K && out.size(0) == M && out.size(1) == N && scale.size(0) == N,
+              "qgemm: shapes");
+  if (M == 0) return;
+  TORCH_CHECK(akap::qgemm_supported(M, N, K, x.stride(0), out.stride(0)),
+              "qgemm: needs M <= 256, K % 64 == 0, N % 8 == 0 and 16-byte aligned rows");
+  TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0 && (uintptr_t)wq.data_ptr() % 16 == 0 &&
+              (uintptr_t)out.data_ptr() % 16 == 0 && (uintptr_t)scale.data_ptr() % 16 == 0,
+              "qgemm: 16-byte aligned base addresses");
+  akap::QGemmArgs a{x.data_ptr(), wq.data_ptr(), scale.data_ptr<float>(), out.data_ptr(),
+                    M, N, K, (int)x.stride(0), (int)out.stride(0)};
+  const c10::DeviceGuard g(x.device());
+  akap::launch_qgemm(a, cur_stream());
+}
+
+// out[N, K] bf16 = bf16(float(wq) * scale[:, None]) (one fp32 multiply, RNE cast)
+void dequant_fp8(Tensor out, Tensor wq, Tensor scale) {
+  CHECK_GPU(wq); CHECK_GPU(scale); CHECK_GPU(out); CHECK_BF16(out);
+  TORCH_CHECK(is_fp8_bytes(wq), "dequant_fp8: wq must be uint8 / float8_e4m3fn");
+  TORCH_CHECK(scale.scalar_type() == at::kFloat, "dequant_fp8: scale must be fp32");
+  TORCH_CHECK(wq.dim() == 2 && out.dim() == 2 && scale.dim() == 1, "dequant_fp8: dims");
+  CHECK_CONTIG(wq); CHECK_CONTIG(out); CHECK_CONTIG(scale);
+  TORCH_CHECK(wq.device() == out.device() && wq.device() == scale.device(),
+              "dequant_fp8: tensors on different devices");
+  const int64_t N = wq.size(0), K = wq.size(1);
+  TORCH_CHECK(out.size(0) == N && out.size(1) == K && scale.size(0) == N, "dequant_fp8: shapes");
+  TORCH_CHECK(K % 16 == 0, "dequant_fp8: K % 16 == 0");
+  TORCH_CHECK((uintptr_t)wq.data_ptr() % 16 == 0 && (uintptr_t)out.data_ptr() % 16 == 0,
+              "dequant_fp8: 16-byte aligned base addresses");
+  const c10::DeviceGuard g(wq.device());
+  akap::launch_dequant_fp8(wq.data_ptr(), scale.data_ptr<float>(), out.data_ptr(), N, (int)K,
+                           cur_stream());
+}
+
 // Narrow-output decode GEMM with the K split inside the workgroup (csrc/kernels/kgemm.hip):
 // out = x @ w^T (rows scaled by rsqrt(ss_in / K + eps) when ss_in is given), epi 0 store,
 // 1 residual/next-norm (out = residual in/out, aout = bf16(out * ln_out), ss_out += row sums).
@@ -1293,6 +1343,8 @@ TORCH_LIBRARY(akap, m) {
       "Tensor? ss_in=None, Tensor(d!)? ss_out=None, Tensor(e!)? aout=None, "
       "Tensor? ln_out=None, int bn=0, int ns=0, Tensor(f!)? counters=None, int bm=64) -> ()");
   m.def("wgemm(Tensor(a!) out, Tensor x, Tensor w) -> ()");
+  m.def("qgemm(Tensor(a!) out, Tensor x, Tensor wq, Tensor scale) -> ()");
+  m.def("dequant_fp8(Tensor(a!) out, Tensor wq, Tensor scale) -> ()");
   m.def("pgemm(Tensor(a!) out, Tensor x, Tensor w, int epi=0, Tensor? offs=None) -> ()");
   m.def("kgemm(Tensor(a!) out, Tensor x, Tensor w, int bm, int epi, float eps, Tensor? ss_in, "
         "Tensor(b!)? ss_out, Tensor(c!)? aout, Tensor? ln_out) -> ()");
@@ -1374,6 +1426,8 @@ TORCH_LIBRARY_IMPL(akap, CUDA, m) {
   m.impl("gemm", &gemm);
   m.impl("dgemm", &dgemm);
   m.impl("wgemm", &wgemm);
+  m.impl("qgemm", &qgemm);
+  m.impl("dequant_fp8", &dequant_fp8);
   m.impl("pgemm", &pgemm);
   m.impl("kgemm", &kgemm);
   m.impl("moe_topk_softmax", &moe_topk_softmax);

@@ -59,11 +59,21 @@ class ModelRunner:
         t0 = time.time()
         self.model = DecoderLM(mcfg, self.device, seed=ecfg.seed, pstate=self.ps,
                                max_model_len=ecfg.max_model_len, init_std=ecfg.init_std,
-                               full_then_shard=ecfg.shard_init == "full")
+                               full_then_shard=ecfg.shard_init == "full",
+                               quantization=ecfg.quantization)
         if ecfg.load_format == "safetensors" and ecfg.weights_path:
             from .weights import load_safetensors_dir
 
             self.model.load_state_dict(load_safetensors_dir(ecfg.weights_path))
+        if ecfg.quantization == "fp8":
+            # after the weights are in place and before the KV cache is sized: the freed bf16
+            # projections go back to the allocator so _derive_num_blocks sees that HBM
+            self.model.quantize_fp8()
+            bf16_gib = self.model.weight_bytes(as_bf16=True) / 2**30
+            if self.is_gpu:
+                torch.cuda.empty_cache()
+            self.log(f"[runner] fp8 weights: {self.model.weight_bytes() / 2**30:.2f} GiB/rank "
+                     f"(bf16 {bf16_gib:.2f} GiB; embedding, LM head and norms stay bf16)")
         self.log(f"[runner] model {mcfg.name} ready in {time.time() - t0:.1f}s "
                  f"({self.model.weight_bytes() / 2**30:.2f} GiB weights/rank)")
         self.bs = ecfg.block_size
@@ -729,6 +739,10 @@ class ModelRunner:
             t1 = time.time()
             tune_ms = [b for b in self.buckets if b >= 16]
             cache = os.environ.get("AKAP_GEMM_TUNE_CACHE")
+            if self.model.quantized:
+                # a quantized model tunes only its bf16 LM head: its plan is neither read from
+                # nor written to the cache file of the bf16 model with the same shapes
+                cache = None
             if cache and self.model.ps.world_size > 1:
                 cache = f"{cache}.rank{self.model.ps.rank}"
             pre_m = self.ecfg.max_num_batched_tokens

@@ -22,6 +22,7 @@ import torch.nn.functional as F
 
 from .. import ops
 from ..ops import reference as ref
+from ..ops.quant import Fp8Weight, quantize_fp8, reserve_scratch
 from ..parallel import comm
 from ..parallel.state import ParallelState, get_state
 from .config import ModelConfig
@@ -70,14 +71,57 @@ class LayerWeights:
     moe: Optional[MoEBlock] = None
 
 
-def _shard_rows(w: torch.Tensor, rank: int, size: int) -> torch.Tensor:
+def _shard_rows(w, rank: int, size: int):
     n = w.shape[0] // size
     return w[rank * n:(rank + 1) * n]
 
 
-def _shard_cols(w: torch.Tensor, rank: int, size: int) -> torch.Tensor:
+def _shard_cols(w, rank: int, size: int):
     n = w.shape[1] // size
     return w[:, rank * n:(rank + 1) * n]
+
+
+PROJECTIONS = ("w_qkv", "w_o", "w_gate_up", "w_down")
+QUANTIZATIONS = (None, "fp8")
+_FP8_BLOCK = 128  # block-scaled checkpoints: one weight_scale_inv per 128 x 128 block
+
+
+def _checkpoint_proj(sd: dict, key: str, quantized: bool):
+    """The projection `key`.weight of a checkpoint: a plain tensor, or an Fp8Weight for a
+    pre-quantized float8_e4m3fn weight with a per-channel ([N, 1] / [N]) or per-tensor (scalar,
+    expanded) `weight_scale`.  A block-scaled weight (`weight_scale_inv`, 128 x 128 blocks) is
+    dequantized to fp32 here and re-quantized per channel by the caller.  `input_scale`
+    (activation scales of W8A8 checkpoints) is not used: activations stay bf16."""
+    w = sd[key + ".weight"]
+    if w.dtype != torch.float8_e4m3fn:
+        return w
+    if not quantized:
+        raise ValueError(f"{key}.weight is float8_e4m3fn: this is an FP8 checkpoint, load it "
+                         f"with --quantization fp8")
+    N, K = w.shape
+    if key + ".weight_scale_inv" in sd:
+        s = sd[key + ".weight_scale_inv"].float()
+        s = s.repeat_interleave(_FP8_BLOCK, 0)[:N].repeat_interleave(_FP8_BLOCK, 1)[:, :K]
+        return w.float() * s
+    if key + ".weight_scale" not in sd:
+        raise ValueError(f"{key}.weight is float8_e4m3fn but the checkpoint has no "
+                         f"{key}.weight_scale")
+    s = sd[key + ".weight_scale"].float().reshape(-1)
+    if s.numel() == 1:
+        s = s.expand(N)
+    elif s.numel() != N:
+        raise ValueError(f"{key}.weight_scale has {s.numel()} values for {N} output channels")
+    return Fp8Weight(w.view(torch.uint8), s.contiguous())
+
+
+def _fuse_rows(parts: list):
+    """Concatenate projections along the output channels: bit-exact for pre-quantized parts
+    (codes and per-channel scales are concatenated), fp32 otherwise."""
+    if all(isinstance(p, Fp8Weight) for p in parts):
+        return Fp8Weight(torch.cat([p.q for p in parts], 0), torch.cat([p.scale for p in parts], 0))
+    if any(isinstance(p, Fp8Weight) or p.dtype == torch.float32 for p in parts):
+        return torch.cat([p.float() for p in parts], 0)
+    return torch.cat(parts, 0)
 
 
 def ipc_safe_alloc_bytes(nbytes: int) -> int:
@@ -113,7 +157,19 @@ class DecoderLM:
     def __init__(self, cfg: ModelConfig, device: torch.device | str = "cpu",
                  dtype: torch.dtype = torch.bfloat16, seed: int = 0,
                  pstate: Optional[ParallelState] = None, max_model_len: int = 4096,
-                 full_then_shard: bool = False, init_std: float = 0.02):
+                 full_then_shard: bool = False, init_std: float = 0.02,
+                 quantization: Optional[str] = None):
+        if quantization == "none":
+            quantization = None
+        if quantization not in QUANTIZATIONS:
+            raise ValueError(f"unknown quantization {quantization!r} (none | fp8)")
+        if quantization == "fp8" and cfg.is_moe:
+            raise ValueError(f"{cfg.name}: fp8 weight quantization covers dense models only "
+                             f"(MoE experts are not quantized)")
+        # "fp8": load_state_dict accepts FP8 checkpoints and quantizes plain ones; a model
+        # built from random weights is quantized by quantize_fp8()
+        self.quantization = quantization
+        self.quantized = False  # some layer projection is an Fp8Weight
         self.cfg = cfg
         self.init_std = init_std
         self.device = torch.device(device)
@@ -221,18 +277,45 @@ class DecoderLM:
         """Decode step free of host syncs (capturable in a hipGraph)."""
         return all(l.moe is None or l.moe.graph_safe for l in self.layers)
 
-    def weight_bytes(self) -> int:
+    def weight_bytes(self, as_bf16: bool = False) -> int:
+        """bf16 tensors at 2 bytes per element; a quantized projection [N, K] counts
+        N * K + 4 * N (codes + fp32 scales), or what it would take in bf16 with as_bf16."""
         n = self.embed.numel() + self.final_norm.numel()
+        q = 0
         if self.lm_head is not self.embed:
             n += self.lm_head.numel()
         for lw in self.layers:
             for t in (lw.ln1, lw.ln2, lw.w_qkv, lw.w_o, lw.q_norm, lw.k_norm, lw.w_gate_up,
                       lw.w_down):
-                if t is not None:
+                if isinstance(t, Fp8Weight):
+                    q += 2 * t.numel() if as_bf16 else t.nbytes
+                elif t is not None:
                     n += t.numel()
             if lw.moe is not None:
                 n += lw.moe.numel()
-        return n * 2
+        return n * 2 + q
+
+    @torch.no_grad()
+    def quantize_fp8(self) -> None:
+        """Replace every dense layer's projections by per-channel e4m3fn Fp8Weights, one layer
+        at a time, dropping each bf16 tensor as it goes.  Embedding, LM head and norms stay
+        bf16, as in published FP8 checkpoints.  Also reserves the dequantization scratch the
+        prefill path uses (ops.quant), sized to the largest quantized weight."""
+        if any(lw.moe is not None for lw in self.layers):
+            raise ValueError(f"{self.cfg.name}: fp8 weight quantization covers dense models "
+                             f"only (MoE experts are not quantized)")
+        largest = 0
+        for lw in self.layers:
+            for name in PROJECTIONS:
+                w = getattr(lw, name)
+                if not isinstance(w, Fp8Weight):
+                    setattr(lw, name, None)
+                    w = quantize_fp8(w)
+                    setattr(lw, name, w)
+                largest = max(largest, w.numel())
+        self.quantization = "fp8"
+        self.quantized = True
+        reserve_scratch(largest, self.device)
 
     def hf_state_dict(self) -> dict:
         """This (unsharded, tp=1) model's weights under HF names, un-fusing QKV and gate|up
@@ -247,14 +330,23 @@ class DecoderLM:
         if not cfg.tie_embeddings:
             sd["lm_head.weight"] = self.lm_head[:n].clone()
         q, kv = self.hq * D, self.hkv * D
+
+        def put(key: str, w, a: int = 0, b: Optional[int] = None) -> None:
+            # rows [a, b) of a projection; quantized: float8_e4m3fn codes + [N, 1] fp32 scales
+            if isinstance(w, Fp8Weight):
+                sd[key + ".weight"] = w.q[a:b].clone().view(torch.float8_e4m3fn)
+                sd[key + ".weight_scale"] = w.scale[a:b].clone().reshape(-1, 1)
+            else:
+                sd[key + ".weight"] = w[a:b].clone()
+
         for i, lw in enumerate(self.layers):
             p = f"model.layers.{i}."
             sd[p + "input_layernorm.weight"] = lw.ln1.clone()
             sd[p + "post_attention_layernorm.weight"] = lw.ln2.clone()
-            sd[p + "self_attn.q_proj.weight"] = lw.w_qkv[:q].clone()
-            sd[p + "self_attn.k_proj.weight"] = lw.w_qkv[q:q + kv].clone()
-            sd[p + "self_attn.v_proj.weight"] = lw.w_qkv[q + kv:].clone()
-            sd[p + "self_attn.o_proj.weight"] = lw.w_o.clone()
+            put(p + "self_attn.q_proj", lw.w_qkv, 0, q)
+            put(p + "self_attn.k_proj", lw.w_qkv, q, q + kv)
+            put(p + "self_attn.v_proj", lw.w_qkv, q + kv)
+            put(p + "self_attn.o_proj", lw.w_o)
             if lw.q_norm is not None:
                 sd[p + "self_attn.q_norm.weight"] = lw.q_norm.clone()
                 sd[p + "self_attn.k_norm.weight"] = lw.k_norm.clone()
@@ -262,14 +354,41 @@ class DecoderLM:
                 sd.update(lw.moe.hf_state_dict(p))
             else:
                 F_ = lw.w_gate_up.shape[0] // 2
-                sd[p + "mlp.gate_proj.weight"] = lw.w_gate_up[:F_].clone()
-                sd[p + "mlp.up_proj.weight"] = lw.w_gate_up[F_:].clone()
-                sd[p + "mlp.down_proj.weight"] = lw.w_down.clone()
+                put(p + "mlp.gate_proj", lw.w_gate_up, 0, F_)
+                put(p + "mlp.up_proj", lw.w_gate_up, F_)
+                put(p + "mlp.down_proj", lw.w_down)
         return sd
 
+    def _set_proj(self, lw: LayerWeights, name: str, src) -> None:
+        """Store one (fused, sharded) projection.  bf16 model: copy into the existing tensor.
+        fp8 model: a pre-quantized source is kept bit for bit (no bf16 detour); any other
+        source is quantized per channel from its own precision."""
+        cur = getattr(lw, name)
+        if tuple(src.shape) != tuple(cur.shape):
+            raise ValueError(f"{name}: checkpoint shape {tuple(src.shape)} != model "
+                             f"{tuple(cur.shape)}")
+        if self.quantization != "fp8":
+            cur.copy_(src.to(cur.dtype))
+            return
+        setattr(lw, name, None)  # drop the old weight before the new one is resident
+        if not isinstance(src, Fp8Weight):
+            src = quantize_fp8(src.to(self.device))
+        setattr(lw, name, src.to(self.device))
+        self.quantized = True
+        reserve_scratch(src.numel(), self.device)
+
     def load_state_dict(self, sd: dict) -> None:
-        """Load HF-named tensors (safetensors from the model PVC) into the fused layout."""
+        """Load HF-named tensors (safetensors from the model PVC) into the fused layout.
+        With quantization "fp8" the projections may be plain (quantized here), pre-quantized
+        float8_e4m3fn + `weight_scale`, or block-scaled (`weight_scale_inv`)."""
         cfg, tp, r = self.cfg, self.ps.tp_size, self.ps.tp_rank
+        fp8 = self.quantization == "fp8"
+        if not fp8:
+            for k in sd:
+                if k.endswith((".weight_scale", ".weight_scale_inv")):
+                    raise ValueError(f"checkpoint key {k}: this is an FP8 checkpoint, load it "
+                                     f"with --quantization fp8")
+        proj = lambda key: _checkpoint_proj(sd, key, fp8)  # noqa: E731
         cp = lambda dst, src: dst.copy_(src.to(dst.dtype))  # noqa: E731
         emb = sd["model.embed_tokens.weight"]
         n = self.vocab_end - self.vocab_start
@@ -278,23 +397,23 @@ class DecoderLM:
             p = f"model.layers.{i}."
             cp(lw.ln1, sd[p + "input_layernorm.weight"])
             cp(lw.ln2, sd[p + "post_attention_layernorm.weight"])
-            q = _shard_rows(sd[p + "self_attn.q_proj.weight"], r, tp)
+            q = _shard_rows(proj(p + "self_attn.q_proj"), r, tp)
             k0, k1 = self._kv_head_range()
             D = self.D
-            k = sd[p + "self_attn.k_proj.weight"][k0 * D:k1 * D]
-            v = sd[p + "self_attn.v_proj.weight"][k0 * D:k1 * D]
-            cp(lw.w_qkv, torch.cat([q, k, v], 0))
-            cp(lw.w_o, _shard_cols(sd[p + "self_attn.o_proj.weight"], r, tp))
+            k = proj(p + "self_attn.k_proj")[k0 * D:k1 * D]
+            v = proj(p + "self_attn.v_proj")[k0 * D:k1 * D]
+            self._set_proj(lw, "w_qkv", _fuse_rows([q, k, v]))
+            self._set_proj(lw, "w_o", _shard_cols(proj(p + "self_attn.o_proj"), r, tp))
             if lw.q_norm is not None:
                 cp(lw.q_norm, sd[p + "self_attn.q_norm.weight"])
                 cp(lw.k_norm, sd[p + "self_attn.k_norm.weight"])
             if lw.moe is not None:
                 lw.moe.load_state_dict(sd, p)
             else:
-                g_ = _shard_rows(sd[p + "mlp.gate_proj.weight"], r, tp)
-                u_ = _shard_rows(sd[p + "mlp.up_proj.weight"], r, tp)
-                cp(lw.w_gate_up, torch.cat([g_, u_], 0))
-                cp(lw.w_down, _shard_cols(sd[p + "mlp.down_proj.weight"], r, tp))
+                g_ = _shard_rows(proj(p + "mlp.gate_proj"), r, tp)
+                u_ = _shard_rows(proj(p + "mlp.up_proj"), r, tp)
+                self._set_proj(lw, "w_gate_up", _fuse_rows([g_, u_]))
+                self._set_proj(lw, "w_down", _shard_cols(proj(p + "mlp.down_proj"), r, tp))
         cp(self.final_norm, sd["model.norm.weight"])
         if not cfg.tie_embeddings:
             cp(self.lm_head[:n], sd["lm_head.weight"][self.vocab_start:self.vocab_end])
@@ -385,8 +504,9 @@ class DecoderLM:
         cfg = self.cfg
         T = input_ids.shape[0]
         eps = cfg.rms_eps
+        # (the fused dgemm chain is bf16-only: a quantized model takes the unfused path below)
         if (not batch.is_prefill and FUSED_DECODE and FUSED_GEMM and self.device.type == "cuda"
-                and all(l.moe is None for l in self.layers)):
+                and not self.quantized and all(l.moe is None for l in self.layers)):
             from ..ops import gemm_tuner
 
             plan = gemm_tuner.fused_plan(T)
@@ -401,7 +521,7 @@ class DecoderLM:
                 h, residual = ops.fused_add_rms_norm(x, residual, lw.ln1, eps)
             qkv = ops.linear(h, lw.w_qkv)
             attn = torch.empty(T, self.hq, self.D, dtype=self.dtype, device=self.device)
-            if not batch.is_prefill and PREFETCH_WEIGHTS:
+            if not batch.is_prefill and PREFETCH_WEIGHTS and not self.quantized:
                 # warm this layer's remaining GEMM weights (+ the next QKV) in MALL before
                 # the HBM-bound attention stream; the latency-bound GEMMs then hit cache
                 nxt = self.layers[li + 1].w_qkv if li + 1 < len(self.layers) else None

@@ -19,6 +19,7 @@ import torch
 
 from . import reference as ref
 from .gemm_variant import Variant
+from .quant import Fp8Weight, linear_fp8, quantize_fp8  # noqa: F401
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _LIB = os.path.join(_PKG, "_C.so")
@@ -303,7 +304,9 @@ def _use_pgemm(x: torch.Tensor, w: torch.Tensor, silu: bool = False) -> bool:
 def linear_silu(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     """silu(x @ gate.T) * (x @ up.T) for the [gate; up] weight w [2F, K]: one pgemm launch
     with the SwiGLU epilogue for prefill-sized M (no [M, 2F] intermediate round trip through
-    HBM), else linear + silu_and_mul."""
+    HBM), else linear + silu_and_mul.  An Fp8Weight takes linear + silu_and_mul."""
+    if isinstance(w, Fp8Weight):
+        return silu_and_mul(linear_fp8(x, w))
     if _use_pgemm(x, w, silu=True):
         load_native(required=True)
         return pgemm(x, w, silu=True)
@@ -313,7 +316,10 @@ def linear_silu(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
 def linear(x: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """y = x @ w.T.  Decode-sized M on the GPU -> the hand-written MFMA GEMM (small tiles +
     split-K to fill 256 CUs); large M (prefill) -> hipBLASLt via torch, or the hand-written
-    256 x 256 pgemm where it measured faster (AKAP_PREFILL_GEMM)."""
+    256 x 256 pgemm where it measured faster (AKAP_PREFILL_GEMM).  w may be an Fp8Weight
+    (ops/quant.py): M <= 256 -> the fp8-weight qgemm, else dequantize + this bf16 path."""
+    if isinstance(w, Fp8Weight):
+        return linear_fp8(x, w, out=out)
     M = x.shape[0]
     split = None
     if _use_pgemm(x, w):

@@ -275,7 +275,8 @@ def tune_model(model, Ms: Sequence[int], log=print) -> dict:
     for lw in model.layers:
         for name in ("w_qkv", "w_o", "w_gate_up", "w_down"):
             w = getattr(lw, name, None)
-            if w is not None:
+            # a quantized projection (ops.quant.Fp8Weight) runs qgemm, which has no candidates
+            if isinstance(w, torch.Tensor):
                 groups.setdefault((name, tuple(w.shape)), []).append(w)
     summary = {}
     anchors = anchor_ms(Ms)
@@ -353,6 +354,8 @@ def tune_fused(model, Ms: Sequence[int], log=print, splits=(1, 2, 4, 8), pfs=(2,
     from . import EPI_SILU
 
     if not model.layers or any(getattr(l, "moe", None) is not None for l in model.layers):
+        return {}
+    if getattr(model, "quantized", False):  # the fused chain is bf16-only
         return {}
     if verbose is None:  # AKAP_GEMM_TUNE_VERBOSE=1: per-role winners and runners-up
         import os
@@ -455,6 +458,9 @@ def tune_prefill(model, M: int, log=print, margin: float = 0.02) -> dict:
     layer weights (rotating through the layers inside one captured graph)."""
     from . import pgemm_supported, silu_and_mul
 
+    if getattr(model, "quantized", False):
+        # prefill of a quantized model runs the library GEMM on the dequantization scratch
+        return {}
     groups: dict = {}
     for lw in model.layers:
         for name in ("w_qkv", "w_o", "w_gate_up", "w_down"):
