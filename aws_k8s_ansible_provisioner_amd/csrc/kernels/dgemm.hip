@@ -31,17 +31,13 @@
 // registers (a compile-time ring, loop unrolled by PF so every register index is static and
 // the compiler's vmcnt counting stays exact), because at decode sizes each block's K loop is
 // a chain of HBM/L2 round trips, not math.
-#include "common.h"
-#include "kernels.h"
+#include <cstdlib>
+
+#include "gemm_common.h"
 
 namespace akap {
 
 constexpr int DBM = 64, DBN = 64, DBK = 64;
-constexpr int kDgSc1 = 16;  // buffer op cache bits: sc1 (write-through stores, L1-bypass loads)
-
-__device__ __forceinline__ int dswz(int row, int chunk) { return row * 8 + (chunk ^ (row & 7)); }
-
-__device__ __forceinline__ float silu_bf(float g) { return bf2f(f2bf(g / (1.f + __expf(-g)))); }
 
 // SPL: 0 whole K, 1 fp32 partial slabs for the separate reduce pass, 2 in-launch combine of
 // the S slices (plain prologue only): fragment-native sc1 slabs + a per-tile last-arriver ticket,
@@ -144,8 +140,8 @@ __global__ __launch_bounds__(256, 2) void dgemm_kernel(DGemmArgs p) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) av[j] = f2bf(silu_bf(bf2f(sa[q][c][j])) * bf2f(sx[q][c][j]));
       }
-      lds[buf * 1024 + dswz(s_row[c], s_ch)] = av;
-      lds[buf * 1024 + 512 + dswz(s_row[c], s_ch)] = sb[q][c];
+      lds[buf * 1024 + swz8(s_row[c], s_ch)] = av;
+      lds[buf * 1024 + 512 + swz8(s_row[c], s_ch)] = sb[q][c];
     }
   };
 
@@ -160,8 +156,8 @@ __global__ __launch_bounds__(256, 2) void dgemm_kernel(DGemmArgs p) {
       bf16x8 af[2], bfr[2];
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        af[i] = lds[buf * 1024 + dswz(wm * 32 + i * 16 + fr, ks * 4 + fg)];
-        bfr[i] = lds[buf * 1024 + 512 + dswz(wn * 32 + i * 16 + fr, ks * 4 + fg)];
+        af[i] = lds[buf * 1024 + swz8(wm * 32 + i * 16 + fr, ks * 4 + fg)];
+        bfr[i] = lds[buf * 1024 + 512 + swz8(wn * 32 + i * 16 + fr, ks * 4 + fg)];
       }
 #pragma unroll
       for (int i = 0; i < 2; ++i)
@@ -242,20 +238,11 @@ __global__ __launch_bounds__(256, 2) void dgemm_kernel(DGemmArgs p) {
 #pragma unroll
     for (int f = 0; f < NF; ++f)
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[f >> 1][f & 1]), rs,
-                                             (int)((mine + (size_t)f * 256) * 16), 0, kDgSc1);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains its stores
-    __syncthreads();
-    int* flag = reinterpret_cast<int*>(rowss);  // the plain prologue leaves rowss unused
-    if (tid == 0) {
-      int* ticket = p.counters + (size_t)lt * kCtrStride;
-      const int prev = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED,
-                                              __HIP_MEMORY_SCOPE_AGENT);
-      const int last = prev == S - 1;
-      if (last) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      *flag = last;
-    }
-    __syncthreads();
-    if (*flag == 0) return;
+                                             (int)((mine + (size_t)f * 256) * 16), 0, kSc1);
+    // the plain prologue leaves rowss unused: its first word is the "this block combines" flag
+    if (!splitk_last_arriver<S>(p.counters + (size_t)lt * kCtrStride,
+                                reinterpret_cast<int*>(rowss)))
+      return;
     // all S slabs (own included), every load issued before any sum; sc1 loads bypass the
     // per-XCD caches a slice on another XCD could not have written through
     const size_t t0 = (size_t)lt * tile_stride + tid;
@@ -266,7 +253,7 @@ __global__ __launch_bounds__(256, 2) void dgemm_kernel(DGemmArgs p) {
       for (int f = 0; f < NF; ++f)
         v[z][f] = __builtin_bit_cast(
             f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                       rs, (int)((t0 + (size_t)z * zs + (size_t)f * 256) * 16), 0, kDgSc1));
+                       rs, (int)((t0 + (size_t)z * zs + (size_t)f * 256) * 16), 0, kSc1));
 #pragma unroll
     for (int f = 0; f < NF; ++f) {
       f32x4 s = v[0][f];
@@ -324,13 +311,9 @@ __global__ __launch_bounds__(256, 2) void dgemm_kernel(DGemmArgs p) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
           const int col = n0 + wn * 32 + j * 16 + fr;
-          if (row_ok && col < p.N) {
-            const bf16 s = f2bf(bf2f(f2bf(acc[i][j][r] * scale)) + bf2f(rold[i][r][j]));
-            Y[(size_t)row * p.ldy + col] = s;
-            const float f = bf2f(s);
-            Ao[(size_t)row * p.N + col] = f2bf(f * bf2f(lnv[j]));
-            q2 += f * f;
-          }
+          if (row_ok && col < p.N)
+            q2 += resnorm1(acc[i][j][r], scale, rold[i][r][j], lnv[j],
+                           Y[(size_t)row * p.ldy + col], Ao[(size_t)row * p.N + col]);
         }
         // the 16 lanes of this row (same fg) hold its 16 columns of each sub-tile
         q2 += __shfl_xor(q2, 1, kWave);
@@ -395,14 +378,7 @@ __global__ __launch_bounds__(256) void dgemm_reduce_kernel(DGemmArgs p) {
       const bf16x4 old = *yp;
       const bf16x4 g = *reinterpret_cast<const bf16x4*>(static_cast<const bf16*>(p.ln_out) + col);
       bf16x4 o, a;
-      float q2 = 0.f;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        o[j] = f2bf(bf2f(f2bf(s[j] * scale)) + bf2f(old[j]));
-        const float f = bf2f(o[j]);
-        a[j] = f2bf(f * bf2f(g[j]));
-        q2 += f * f;
-      }
+      float q2 = resnorm4(s, scale, old, g, o, a);
       *yp = o;
       *reinterpret_cast<bf16x4*>(static_cast<bf16*>(p.Aout) + (size_t)row * N + col) = a;
       q2 = wave_sum(q2);
@@ -492,13 +468,7 @@ __global__ __launch_bounds__(256) void dgemm_reduce_resnorm_row_kernel(DGemmArgs
   for (int k = 0; k < NI; ++k) {
     const int c = k * 1024 + threadIdx.x * 4;
     bf16x4 o, a;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      o[j] = f2bf(bf2f(f2bf(acc[k][j] * scale)) + bf2f(old[k][j]));
-      const float f = bf2f(o[j]);
-      a[j] = f2bf(f * bf2f(g[k][j]));
-      q2 += f * f;
-    }
+    q2 = resnorm4(acc[k], scale, old[k], g[k], o, a, q2);
     *reinterpret_cast<bf16x4*>(Y + (size_t)row * p.ldy + c) = o;
     *reinterpret_cast<bf16x4*>(Ao + (size_t)row * N + c) = a;
   }
@@ -568,6 +538,26 @@ void launch_dgemm_reduce(const DGemmArgs& p, int pro, int splitk, hipStream_t st
   } else {
     reduce_s<0, EPI_STORE>(p, splitk, b, st);
   }
+}
+
+// AKAP_GEMM_STAGGER: unset -> 0 (every workgroup walks K from its slice's start)
+int gemm_stagger_default() {
+  static const int v = [] {
+    const char* e = std::getenv("AKAP_GEMM_STAGGER");
+    return e == nullptr ? 0 : std::atoi(e);
+  }();
+  return v;
+}
+
+// AKAP_WEIGHT_NT: unset -> -1 (gdgemm weights non-temporal, kgemm default policy: measured
+// Llama-3-8B +0.7 % on both A/B pairs, Qwen3-0.6B -0.65 % with kgemm nt too,
+// profiles/r3_weight_nt_ab.log); 1 -> both non-temporal; 0 -> neither
+int weight_nt_default() {
+  static const int v = [] {
+    const char* e = std::getenv("AKAP_WEIGHT_NT");
+    return e == nullptr ? -1 : (std::atoi(e) == 1 ? 1 : 0);
+  }();
+  return v;
 }
 
 void launch_dgemm(const DGemmArgs& a, int pro, int splitk, int pf, hipStream_t st) {

@@ -37,64 +37,20 @@
 //          ticket and sums the S slabs with sc1 loads, then runs the epilogue.  No second
 //          launch, so the GEMM -> reduce kernel boundary (~1.5 us) and the reduce body go away,
 //          and split-K becomes legal for the SwiGLU epilogue too.
-#include <cstdlib>
-
-#include "common.h"
-#include "kernels.h"
+#include "gemm_common.h"
 
 namespace akap {
 
 constexpr int GBK = 64;
-constexpr int kGdSc1 = 16;  // buffer op cache bits: sc1 (write-through stores, L1-bypass loads)
-
-__device__ __forceinline__ int gswz(int row, int chunk) { return row * 8 + (chunk ^ (row & 7)); }
 
 // LDS image of a BKT-deep k-step: rows of BKT * 2 bytes in 16-B chunks, XOR-swizzled so the 16
 // lanes of a ds_read_b128 lane group (16 consecutive rows, one chunk) hit 16 distinct 16-B bank
-// positions.  BKT = 64: 8 chunks per row, chunk ^ (row & 7).  BKT = 32: 4 chunks per row (four
-// rows per 256-B bank row), chunk ^ ((row >> 2) & 3).
+// positions.  BKT = 64: swz8.  BKT = 32: 4 chunks per row (four rows per 256-B bank row),
+// chunk ^ ((row >> 2) & 3).
 template <int BKT>
 __device__ __forceinline__ int gswz_t(int row, int chunk) {
-  if constexpr (BKT == 64) return row * 8 + (chunk ^ (row & 7));
+  if constexpr (BKT == 64) return swz8(row, chunk);
   else return row * 4 + (chunk ^ ((row >> 2) & 3));
-}
-
-__device__ __forceinline__ void glds16(const void* g, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0,
-                                   0);
-}
-// the same with the non-temporal policy: once-read decode weights (MI355X_MICROARCH.md
-// nt-weights), never for the activation rows every column tile re-reads
-__device__ __forceinline__ void glds16_nt(const void* g, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0,
-                                   2);
-}
-
-// AKAP_WEIGHT_NT: unset -> -1 (gdgemm weights non-temporal, kgemm default policy: measured
-// Llama-3-8B +0.7 % on both A/B pairs, Qwen3-0.6B -0.65 % with kgemm nt too,
-// profiles/r3_weight_nt_ab.log); 1 -> both non-temporal; 0 -> neither
-int gemm_stagger_default() {
-  static const int v = [] {
-    const char* e = std::getenv("AKAP_GEMM_STAGGER");
-    return e == nullptr ? 0 : std::atoi(e);
-  }();
-  return v;
-}
-
-int weight_nt_default() {
-  static const int v = [] {
-    const char* e = std::getenv("AKAP_WEIGHT_NT");
-    return e == nullptr ? -1 : (std::atoi(e) == 1 ? 1 : 0);
-  }();
-  return v;
-}
-
-template <int N_>
-__device__ __forceinline__ void wait_vm() {
-  if constexpr (N_ >= 63) asm volatile("s_waitcnt vmcnt(63)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_) : "memory");
 }
 
 // BKT: k-step depth (64 in every served variant).  Measured and removed: a 6-slot ring of
@@ -167,7 +123,8 @@ __global__ __launch_bounds__(64 * NW, OCC) void gdgemm_kernel(DGemmArgs p) {
     for (int i = 0; i < GA; ++i) glds16(asrc[i] + k0, slot + (w * GA + i) * 64);
     if (p.ntw != 0) {
 #pragma unroll
-      for (int i = 0; i < GW; ++i) glds16_nt(wsrc[i] + k0, slot + GBM * CPR + (w * GW + i) * 64);
+      for (int i = 0; i < GW; ++i)
+        glds16<kAuxNT>(wsrc[i] + k0, slot + GBM * CPR + (w * GW + i) * 64);
     } else {
 #pragma unroll
       for (int i = 0; i < GW; ++i) glds16(wsrc[i] + k0, slot + GBM * CPR + (w * GW + i) * 64);
@@ -256,20 +213,10 @@ __global__ __launch_bounds__(64 * NW, OCC) void gdgemm_kernel(DGemmArgs p) {
       for (int j = 0; j < JN; ++j)
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[i][j]), rs,
                                                (int)((mine + (size_t)(i * JN + j) * NT) * 16), 0,
-                                               kGdSc1);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // EVERY storing wave drains its stores
-    __syncthreads();
-    int* flag = reinterpret_cast<int*>(&lds[NS * SU]);
-    int* ticket = p.counters + (size_t)lt * kCtrStride;
-    if (tid == 0) {
-      const int prev = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED,
-                                              __HIP_MEMORY_SCOPE_AGENT);
-      const int last = prev == S - 1;
-      if (last) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      *flag = last;
-    }
-    __syncthreads();
-    if (*flag == 0) return;
+                                               kSc1);
+    if (!splitk_last_arriver<S>(p.counters + (size_t)lt * kCtrStride,
+                                reinterpret_cast<int*>(&lds[NS * SU])))
+      return;
     // the combining block sums all S slabs (its own included: one code path, every load
     // issued back to back -- no per-slice runtime condition around a load); sc1 loads miss
     // the (per-XCD, non-coherent) caches a slice on another XCD could not have written through
@@ -277,7 +224,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void gdgemm_kernel(DGemmArgs p) {
 #pragma unroll
     for (int f = 0; f < NF; ++f)
       acc[f / JN][f % JN] = __builtin_bit_cast(
-          f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)((t0 + f * NT) * 16), 0, kGdSc1));
+          f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)((t0 + f * NT) * 16), 0, kSc1));
     // every slice's fragments (NF per slab) requested before any is summed: one round trip
     // past the per-XCD L2 per slab, overlapped
     for (int z = 1; z < S; ++z) {
@@ -286,7 +233,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void gdgemm_kernel(DGemmArgs p) {
       for (int f = 0; f < NF; ++f)
         v[f] = __builtin_bit_cast(
             f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)((t0 + z * zs + f * NT) * 16),
-                                                         0, kGdSc1));
+                                                         0, kSc1));
 #pragma unroll
       for (int f = 0; f < NF; ++f) acc[f / JN][f % JN] += v[f];
     }
@@ -342,8 +289,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void gdgemm_kernel(DGemmArgs p) {
           if (row_ok && vb + 16 + fr < p.N) {
             const float g = bf2f(f2bf(acc[i][2 * jj][r] * scale));
             const float u = bf2f(f2bf(acc[i][2 * jj + 1][r] * scale));
-            const float sg = bf2f(f2bf(g / (1.f + __expf(-g))));
-            Y[(size_t)row * p.ldy + (vb >> 1) + fr] = f2bf(sg * u);
+            Y[(size_t)row * p.ldy + (vb >> 1) + fr] = f2bf(silu_bf(g) * u);
           }
         }
       }

@@ -12,15 +12,11 @@
 //     current tile's MFMAs), XOR-swizzled 16-byte chunks (conflict-free ds_read_b128);
 //   * split-K partials go to an fp32 workspace [S, M, N] summed by a reduce pass
 //     (or consumed directly by the fused residual-add + RMSNorm kernel).
-#include "common.h"
-#include "kernels.h"
+#include "gemm_common.h"
 
 namespace akap {
 
-constexpr int GBM = 64, GBN = 64, GBK = 64;
-
-// LDS tile [64 rows][64 k] bf16 = 8 chunks of 16 B per row; chunk' = chunk ^ (row & 7).
-__device__ __forceinline__ int swz(int row, int chunk) { return row * 8 + (chunk ^ (row & 7)); }
+constexpr int GBM = 64, GBN = 64, GBK = 64;  // LDS tiles [64 rows][64 k] bf16, swz8 chunks
 
 template <bool SPLIT, bool CHECK, bool INREDUCE = false>
 __global__ __launch_bounds__(256) void gemm_bf16_kernel(const bf16* __restrict__ X,
@@ -74,8 +70,8 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(const bf16* __restrict__
   auto sstore = [&](int buf) {
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
-      lds[buf][0][swz(s_row, s_ch + c)] = ra[c];
-      lds[buf][1][swz(s_row, s_ch + c)] = rb[c];
+      lds[buf][0][swz8(s_row, s_ch + c)] = ra[c];
+      lds[buf][1][swz8(s_row, s_ch + c)] = rb[c];
     }
   };
 
@@ -100,8 +96,8 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(const bf16* __restrict__
       bf16x8 af[2], bfr[2];
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        af[i] = lds[cur][0][swz(wm * 32 + i * 16 + fr, ks * 4 + fg)];
-        bfr[i] = lds[cur][1][swz(wn * 32 + i * 16 + fr, ks * 4 + fg)];
+        af[i] = lds[cur][0][swz8(wm * 32 + i * 16 + fr, ks * 4 + fg)];
+        bfr[i] = lds[cur][1][swz8(wn * 32 + i * 16 + fr, ks * 4 + fg)];
       }
 #pragma unroll
       for (int i = 0; i < 2; ++i)

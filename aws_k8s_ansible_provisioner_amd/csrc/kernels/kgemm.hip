@@ -20,8 +20,7 @@
 // the 16 lanes of each ds_read_b128 lane group (rows 0-3, 12-15 at chunk c, rows 4-11 at c+1)
 // land on 16 distinct 16-B bank positions: conflict-free (XOR with row & 7 measured 48 %
 // bank-conflict cycles, profiles/r2_pmc_decode_v2.md).
-#include "common.h"
-#include "kernels.h"
+#include "gemm_common.h"
 
 namespace akap {
 
@@ -29,22 +28,6 @@ constexpr int KBN = 32;    // output columns per workgroup
 constexpr int KST = 256;   // K per stage (4 waves x 64)
 
 __device__ __forceinline__ int kswz(int row, int chunk) { return row * 32 + (chunk ^ (row & 15)); }
-
-__device__ __forceinline__ void kglds16(const void* g, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0,
-                                   0);
-}
-__device__ __forceinline__ void kglds16_nt(const void* g, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0,
-                                   2);
-}
-
-template <int N_>
-__device__ __forceinline__ void kwait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_) : "memory");
-}
 
 // KNS = 4 ring slots: 3 stages (96 KB) in flight (a 5-slot ring lost 0.5 % end to end and was
 // removed, profiles/r3_gemm_m256_deep.log)
@@ -96,8 +79,10 @@ __global__ __launch_bounds__(256, 1) void kgemm_kernel(DGemmArgs p) {
     for (int i = 0; i < G; ++i) {
       // instruction (w, i) stages rows 2 (w G + i) and + 1: X rows below BM, weight rows above
       // (wave-uniform), the weights non-temporal only when asked for (p.ntw == 1)
-      if (p.ntw == 1 && (w * G + i) * 2 >= BM) kglds16_nt(src[i] + k0, slot + (w * G + i) * 64);
-      else kglds16(src[i] + k0, slot + (w * G + i) * 64);
+      if (p.ntw == 1 && (w * G + i) * 2 >= BM)
+        glds16<kAuxNT>(src[i] + k0, slot + (w * G + i) * 64);
+      else
+        glds16(src[i] + k0, slot + (w * G + i) * 64);
     }
   };
 
@@ -125,7 +110,7 @@ __global__ __launch_bounds__(256, 1) void kgemm_kernel(DGemmArgs p) {
   for (int s = 0; s < KNS - 1; ++s)
     if (s < nst) issue(s);
   for (int t = 0; t < nst; ++t) {
-    if (t + KNS - 2 < nst) kwait_vm<G * (KNS - 2)>();
+    if (t + KNS - 2 < nst) wait_vm<G * (KNS - 2)>();
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // stage t landed for every wave; slot t-1 is free
@@ -173,14 +158,7 @@ __global__ __launch_bounds__(256, 1) void kgemm_kernel(DGemmArgs p) {
     *reinterpret_cast<bf16x4*>(Y + (size_t)erow * p.ldy + n0 + ec) = o;
   } else {  // EPI_RESNORM: residual += y; Aout = residual * ln_out; ss_out += row sum of squares
     bf16x4 o, a;
-    float q2 = 0.f;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      o[q] = f2bf(bf2f(f2bf(v[q] * scale)) + bf2f(rold[q]));
-      const float f = bf2f(o[q]);
-      a[q] = f2bf(f * bf2f(lnv[q]));
-      q2 += f * f;
-    }
+    float q2 = resnorm4(v, scale, rold, lnv, o, a);
     // the 8 threads of a row are consecutive lanes
     q2 += __shfl_xor(q2, 1, 8);
     q2 += __shfl_xor(q2, 2, 8);

@@ -17,14 +17,11 @@
 //   SILU     W = [gate; up] (N = 2F) read gate/up-interleaved in 16-row groups (dgemm.hip
 //            EPI_SILU): Y[r, f] = bf16(bf16(silu(g)) * u), Y is [rows, F] -- the SwiGLU of
 //            the expert FFN happens in the w13 GEMM's epilogue.
-#include "common.h"
-#include "kernels.h"
+#include "gemm_common.h"
 
 namespace akap {
 
 constexpr int MBN = 128, MBK = 64;
-
-__device__ __forceinline__ int mswz(int row, int chunk) { return row * 8 + (chunk ^ (row & 7)); }
 
 // BM = rows per tile (32 or 64): 4 waves as WM (= BM/32) x WN (= 4/WM), each owning a
 // 32-row x (128/WN)-col sub-tile = 2 x JN 16x16 MFMA tiles.
@@ -86,9 +83,9 @@ __global__ __launch_bounds__(256, 2) void moe_dgemm_kernel(const bf16* __restric
   constexpr int BUF = (BM + MBN) * 8;
   auto sstore = [&](int q, int buf) {
 #pragma unroll
-    for (int c = 0; c < AR; ++c) lds[buf * BUF + mswz(s_r + 32 * c, s_ch)] = sa[q][c];
+    for (int c = 0; c < AR; ++c) lds[buf * BUF + swz8(s_r + 32 * c, s_ch)] = sa[q][c];
 #pragma unroll
-    for (int c = 0; c < 4; ++c) lds[buf * BUF + BM * 8 + mswz(s_r + 32 * c, s_ch)] = sb[q][c];
+    for (int c = 0; c < 4; ++c) lds[buf * BUF + BM * 8 + swz8(s_r + 32 * c, s_ch)] = sb[q][c];
   };
   f32x4 acc[2][JN];
 #pragma unroll
@@ -100,10 +97,10 @@ __global__ __launch_bounds__(256, 2) void moe_dgemm_kernel(const bf16* __restric
     for (int ks = 0; ks < 2; ++ks) {
       bf16x8 af[2], bfr[JN];
 #pragma unroll
-      for (int i = 0; i < 2; ++i) af[i] = lds[buf * BUF + mswz(wm * 32 + i * 16 + fr, ks * 4 + fg)];
+      for (int i = 0; i < 2; ++i) af[i] = lds[buf * BUF + swz8(wm * 32 + i * 16 + fr, ks * 4 + fg)];
 #pragma unroll
       for (int j = 0; j < JN; ++j)
-        bfr[j] = lds[buf * BUF + BM * 8 + mswz(wn * WCOLS + j * 16 + fr, ks * 4 + fg)];
+        bfr[j] = lds[buf * BUF + BM * 8 + swz8(wn * WCOLS + j * 16 + fr, ks * 4 + fg)];
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -148,8 +145,7 @@ __global__ __launch_bounds__(256, 2) void moe_dgemm_kernel(const bf16* __restric
           if (vb + 16 + fr < N) {
             const float g = bf2f(f2bf(acc[i][2 * jj][r]));
             const float u = bf2f(f2bf(acc[i][2 * jj + 1][r]));
-            const float sg = bf2f(f2bf(g / (1.f + __expf(-g))));
-            Y[(size_t)row * ldy + (vb >> 1) + fr] = f2bf(sg * u);
+            Y[(size_t)row * ldy + (vb >> 1) + fr] = f2bf(silu_bf(g) * u);
           }
         }
       } else if constexpr (SPLIT) {

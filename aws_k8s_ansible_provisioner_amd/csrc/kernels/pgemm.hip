@@ -55,8 +55,7 @@
 // writes act[M, F] = silu(gate) * up directly.
 #include <cstdlib>
 
-#include "common.h"
-#include "kernels.h"
+#include "gemm_common.h"
 
 namespace akap {
 
@@ -67,12 +66,6 @@ constexpr int PG_BUF = 2 * PG_T * 8;  // 16-B units per LDS buffer (A 256 rows +
 
 __device__ __forceinline__ int pg_unit(int row, int chunk) {
   return row * 8 + (chunk ^ ((row >> 1) & 7));
-}
-
-__device__ __forceinline__ void pg_glds(const void* g, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0,
-                                   0);
 }
 
 // LDS hand-off point: every wave's ds_reads of the previous phase retired, then the barrier;
@@ -626,7 +619,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void pgemm_kernel(PGemmArgs p) {
         for (int r = 0; r < 4; ++r) {
           const float g = bf2f(f2bf(acc[i][2 * jj][r]));
           const float u = bf2f(f2bf(acc[i][2 * jj + 1][r]));
-          o[r] = f2bf(bf2f(f2bf(g / (1.f + __expf(-g)))) * u);
+          o[r] = f2bf(silu_bf(g) * u);
         }
         *reinterpret_cast<bf16x4*>(Y + (size_t)row * p.ldy + col) = o;
       }
@@ -670,8 +663,6 @@ __device__ __forceinline__ bool pg_spin_ge(const int* c, int v) {
   return true;
 }
 
-constexpr int kPgSc1 = 16;  // buffer op cache bits: sc1 (write-through stores, L1-bypass loads)
-
 // sum over the `splits` slabs of the f32x4 at byte offset off (slab stride bytes): the sc1
 // loads are issued 8 at a time (each is a round trip past the per-XCD L2, ~1 us; a plain loop
 // over the slices would wait for every one in turn)
@@ -684,7 +675,7 @@ __device__ __forceinline__ f32x4 pg_sum_slabs(__amdgpu_buffer_rsrc_t rs, size_t 
     for (int j = 0; j < 8; ++j)
       v[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
                                            rs, (int)(off + min(q0 + j, splits - 1) * stride), 0,
-                                           kPgSc1));
+                                           kSc1));
 #pragma unroll
     for (int j = 0; j < 8; ++j)
       if (q0 + j < splits) y += v[j];
@@ -703,14 +694,7 @@ __device__ __forceinline__ float pg_epi4(const DGemmArgs& p, int row, int col, f
     const bf16x4 r = *reinterpret_cast<const bf16x4*>(Y + (size_t)row * p.ldy + col);
     const bf16x4 g = *reinterpret_cast<const bf16x4*>(static_cast<const bf16*>(p.ln_out) + col);
     bf16x4 a;
-    float q = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      o[k] = f2bf(bf2f(f2bf(y[k] * scale)) + bf2f(r[k]));
-      const float f = bf2f(o[k]);
-      a[k] = f2bf(f * bf2f(g[k]));
-      q += f * f;
-    }
+    const float q = resnorm4(y, scale, r, g, o, a);
     *reinterpret_cast<bf16x4*>(Y + (size_t)row * p.ldy + col) = o;
     *reinterpret_cast<bf16x4*>(static_cast<bf16*>(p.Aout) + (size_t)row * p.N + col) = a;
     return q;
@@ -730,7 +714,7 @@ __device__ __forceinline__ void pg_epi_silu(const DGemmArgs& p, int row, int col
   for (int k = 0; k < 4; ++k) {
     const float gg = bf2f(f2bf(g[k] * scale));
     const float uu = bf2f(f2bf(u[k] * scale));
-    o[k] = f2bf(bf2f(f2bf(gg / (1.f + __expf(-gg)))) * uu);
+    o[k] = f2bf(silu_bf(gg) * uu);
   }
   *reinterpret_cast<bf16x4*>(static_cast<bf16*>(p.Y) + (size_t)row * p.ldy + col) = o;
 }
@@ -800,7 +784,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void pgemm_sk_kernel(DGemmArgs p, in
       const int r = wm * 128 + i * 16 + fr, c = wn * G::WCOLS + j * 16 + fg * 4;
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[i][j]), rs,
                                              (int)(((size_t)s * SLAB + r * PG_T + c) * 4), 0,
-                                             kPgSc1);
+                                             kSc1);
     }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // EVERY storing wave drains its stores
   __syncthreads();

@@ -25,29 +25,16 @@
 // ds_read_b128 of the fp8 row gives the B operands of both MFMAs (low 8 bytes, high 8 bytes)
 // and the A operands are X chunks 2 fg and 2 fg + 1.  A and B agree on the order, which is all
 // an MFMA needs.
-#include "common.h"
-#include "kernels.h"
+#include "gemm_common.h"
 
 namespace akap {
 
 constexpr int QBK = 64;  // k per wave step
 
-__device__ __forceinline__ int qswz_x(int row, int chunk) { return row * 8 + (chunk ^ (row & 7)); }
-// rows of 64 B: chunk c stored at c ^ g((row >> 2) & 3), g = {0, 2, 3, 1} (wgemm.hip ww_swz)
+// X rows (128 B) use swz8.  W rows of 64 B: chunk c stored at c ^ g((row >> 2) & 3),
+// g = {0, 2, 3, 1} (wgemm.hip ww_swz)
 __device__ __forceinline__ int qswz_g(int row) { return (0x1320 >> (4 * ((row >> 2) & 3))) & 3; }
 __device__ __forceinline__ int qswz_w(int row, int c) { return row * 4 + (c ^ qswz_g(row)); }
-
-template <int AUX>
-__device__ __forceinline__ void qglds16(const void* g, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0,
-                                   AUX);
-}
-
-template <int N_>
-__device__ __forceinline__ void qwait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_) : "memory");
-}
 
 template <int MI, int NJ, int NS>
 __global__ __launch_bounds__(256, 1) void qgemm_kernel(QGemmArgs p) {
@@ -100,10 +87,10 @@ __global__ __launch_bounds__(256, 1) void qgemm_kernel(QGemmArgs p) {
     bf16x8* slot = ring + (s % NS) * SU;
     const int k0 = s * 4 * QBK;
 #pragma unroll
-    for (int i = 0; i < GA; ++i) qglds16<0>(asrc[i] + k0, slot + i * 64);
+    for (int i = 0; i < GA; ++i) glds16(asrc[i] + k0, slot + i * 64);
     // every weight byte is read by one workgroup per row tile: non-temporal, as wgemm.hip
 #pragma unroll
-    for (int j = 0; j < GW; ++j) qglds16<2>(wsrc[j] + k0, slot + BM * 8 + j * 64);
+    for (int j = 0; j < GW; ++j) glds16<kAuxNT>(wsrc[j] + k0, slot + BM * 8 + j * 64);
   };
 
   f32x4 acc[MI][NJ];
@@ -118,7 +105,7 @@ __global__ __launch_bounds__(256, 1) void qgemm_kernel(QGemmArgs p) {
   for (int t = 0; t < n; ++t) {
     // retire this wave's DMAs of step t (steps t+1 .. t+NS-2 stay in flight when they exist);
     // the reads below are of this wave's own DMAs, so no barrier is needed
-    if (t + NS - 2 < n) qwait_vm<G * (NS - 2)>();
+    if (t + NS - 2 < n) wait_vm<G * (NS - 2)>();
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // step t-1's fragment reads returned
     if (t + NS - 1 < n) issue(t + NS - 1);              // ... so its slot can be refilled
@@ -127,8 +114,8 @@ __global__ __launch_bounds__(256, 1) void qgemm_kernel(QGemmArgs p) {
     bf16x8 a0[MI], a1[MI];
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
-      a0[i] = slot[qswz_x(i * 16 + fr, 2 * fg)];
-      a1[i] = slot[qswz_x(i * 16 + fr, 2 * fg + 1)];
+      a0[i] = slot[swz8(i * 16 + fr, 2 * fg)];
+      a1[i] = slot[swz8(i * 16 + fr, 2 * fg + 1)];
     }
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {

@@ -22,8 +22,7 @@
 // the LM head writes 78 MB of logits.
 #include <cstdlib>
 
-#include "common.h"
-#include "kernels.h"
+#include "gemm_common.h"
 
 namespace akap {
 
@@ -44,21 +43,7 @@ struct WCfg {
   static constexpr int EP = WC + 8;            // epilogue LDS row pitch (bf16), de-conflicted
 };
 
-__device__ __forceinline__ int wswz(int row, int chunk) { return row * 8 + (chunk ^ (row & 7)); }
-
-template <int AUX = 0>
-__device__ __forceinline__ void wglds16(const void* g, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0,
-                                   AUX);
-}
-
-template <int N_>
-__device__ __forceinline__ void wwait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_) : "memory");
-}
-
-// NTW: the weight stream's DMAs carry the non-temporal policy (aux = 2): every weight byte is
+// NTW: the weight stream's DMAs carry the non-temporal policy (kAuxNT): every weight byte is
 // read by exactly one workgroup, once
 template <int WM, bool NTW = false>
 __global__ __launch_bounds__(512, 2) void wgemm_kernel(WGemmArgs p) {
@@ -94,10 +79,10 @@ __global__ __launch_bounds__(512, 2) void wgemm_kernel(WGemmArgs p) {
     bf16x8* slot = lds + (step % WNS) * C::SU;
     const int k0 = step * WBK;
 #pragma unroll
-    for (int i = 0; i < C::GA; ++i) wglds16(asrc[i] + k0, slot + (w * C::GA + i) * 64);
+    for (int i = 0; i < C::GA; ++i) glds16(asrc[i] + k0, slot + (w * C::GA + i) * 64);
 #pragma unroll
     for (int i = 0; i < C::GW; ++i)
-      wglds16<NTW ? 2 : 0>(wsrc[i] + k0, slot + C::BM * 8 + (w * C::GW + i) * 64);
+      glds16<NTW ? kAuxNT : 0>(wsrc[i] + k0, slot + C::BM * 8 + (w * C::GW + i) * 64);
   };
 
   f32x4 acc[4][C::JN];
@@ -111,7 +96,7 @@ __global__ __launch_bounds__(512, 2) void wgemm_kernel(WGemmArgs p) {
     if (s < nk) issue(s);
   for (int t = 0; t < nk; ++t) {
     // retire this thread's DMAs of step t (step t+1 stays in flight when it exists)
-    if (t + 1 < nk) wwait_vm<C::G>();
+    if (t + 1 < nk) wait_vm<C::G>();
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // every wave's DMAs of step t landed; slot t-1 is free
@@ -121,10 +106,10 @@ __global__ __launch_bounds__(512, 2) void wgemm_kernel(WGemmArgs p) {
     for (int ks = 0; ks < 2; ++ks) {
       bf16x8 af[4], bfr[C::JN];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) af[i] = slot[wswz(wm * 64 + i * 16 + fr, ks * 4 + fg)];
+      for (int i = 0; i < 4; ++i) af[i] = slot[swz8(wm * 64 + i * 16 + fr, ks * 4 + fg)];
 #pragma unroll
       for (int j = 0; j < C::JN; ++j)
-        bfr[j] = slot[C::BM * 8 + wswz(wn * C::WC + j * 16 + fr, ks * 4 + fg)];
+        bfr[j] = slot[C::BM * 8 + swz8(wn * C::WC + j * 16 + fr, ks * 4 + fg)];
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -217,10 +202,10 @@ __global__ __launch_bounds__(512, 1) void wgemm_wide_kernel(WGemmArgs p) {
     bf16x8* slot = lds + (step % NS) * SU;
     const int k0 = step * BK;
 #pragma unroll
-    for (int i = 0; i < GA; ++i) wglds16(asrc[i] + k0, slot + (w * GA + i) * 64);
+    for (int i = 0; i < GA; ++i) glds16(asrc[i] + k0, slot + (w * GA + i) * 64);
 #pragma unroll
     for (int i = 0; i < GW; ++i)
-      wglds16<NTW ? 2 : 0>(wsrc[i] + k0, slot + BM * 4 + (w * GW + i) * 64);
+      glds16<NTW ? kAuxNT : 0>(wsrc[i] + k0, slot + BM * 4 + (w * GW + i) * 64);
   };
 
   f32x4 acc[4][JN];
@@ -234,8 +219,8 @@ __global__ __launch_bounds__(512, 1) void wgemm_wide_kernel(WGemmArgs p) {
     if (s < nk) issue(s);
   for (int t = 0; t < nk; ++t) {
     // retire step t (steps t+1, t+2 stay in flight when they exist)
-    if (t + 2 < nk) wwait_vm<2 * G>();
-    else if (t + 1 < nk) wwait_vm<G>();
+    if (t + 2 < nk) wait_vm<2 * G>();
+    else if (t + 1 < nk) wait_vm<G>();
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // every wave's DMAs of step t landed; slot t-1 is free

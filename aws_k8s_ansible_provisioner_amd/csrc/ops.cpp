@@ -371,18 +371,64 @@ static int device_cus(int dev) {
   return cached[dev];
 }
 
+// The checks and DGemmArgs fields dgemm() and kgemm() share: bf16 GPU operands with aligned rows,
+// out / x / w pointers, sizes and strides, eps, the epilogue, the process-default weight policy
+// and K stagger, the optional ss_in row scale and the EPI_RESNORM operands.  `op` prefixes the
+// messages.
+static akap::DGemmArgs dgemm_args(const char* op, const Tensor& out, const Tensor& x,
+                                  const Tensor& w, double eps, int64_t epi,
+                                  const std::optional<Tensor>& ss_in,
+                                  const std::optional<Tensor>& ss_out,
+                                  const std::optional<Tensor>& aout,
+                                  const std::optional<Tensor>& ln_out) {
+  CHECK_GPU(x); CHECK_BF16(x); CHECK_BF16(w); CHECK_BF16(out);
+  CHECK_LAST_CONTIG(x); CHECK_LAST_CONTIG(w); CHECK_LAST_CONTIG(out);
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && out.dim() == 2, op, ": 2-D tensors");
+  const int M = x.size(0), N = w.size(0), K = w.size(1);
+  TORCH_CHECK(x.stride(0) % 8 == 0 && w.stride(0) % 8 == 0 && out.stride(0) % 4 == 0,
+              op, ": 16-byte aligned rows");
+  akap::DGemmArgs a{};
+  a.ntw = akap::weight_nt_default();
+  a.stag = akap::gemm_stagger_default();
+  a.X = x.data_ptr();
+  a.W = w.data_ptr();
+  a.Y = out.data_ptr();
+  a.M = M; a.N = N; a.K = K;
+  a.ldx = x.stride(0); a.ldw = w.stride(0); a.ldy = out.stride(0);
+  a.eps = (float)eps;
+  a.epi = (int)epi;
+  if (ss_in) {
+    TORCH_CHECK(ss_in->scalar_type() == at::kFloat && ss_in->is_cuda() && ss_in->numel() >= M,
+                op, ": ss_in fp32 [M]");
+    a.ss_in = ss_in->data_ptr<float>();
+  }
+  if (epi == akap::EPI_RESNORM) {
+    TORCH_CHECK(ss_out && aout && ln_out, op, " resnorm epilogue: ss_out, aout, ln_out");
+    TORCH_CHECK(ss_out->scalar_type() == at::kFloat && ss_out->numel() >= M, "ss_out fp32 [M]");
+    CHECK_BF16(*aout); CHECK_CONTIG(*aout); CHECK_BF16(*ln_out);
+    TORCH_CHECK(aout->numel() == (int64_t)M * N && ln_out->numel() == N,
+                op, " resnorm: aout [M, N], ln_out [N]");
+    TORCH_CHECK(out.stride(0) == N, op, " resnorm: residual must be dense");
+    a.ss_out = ss_out->data_ptr<float>();
+    a.Aout = aout->data_ptr();
+    a.ln_out = ln_out->data_ptr();
+  }
+  return a;
+}
+
 void dgemm(Tensor out, Tensor x, Tensor w, Tensor ws, int64_t pro, int64_t splitk, int64_t pf,
            std::optional<Tensor> r, std::optional<Tensor> rout, std::optional<Tensor> ln,
            double eps, int64_t epi, std::optional<Tensor> ss_in, std::optional<Tensor> ss_out,
            std::optional<Tensor> aout, std::optional<Tensor> ln_out, int64_t bn, int64_t ns,
            std::optional<Tensor> counters, int64_t bm) {
-  CHECK_GPU(x); CHECK_BF16(x); CHECK_BF16(w); CHECK_BF16(out);
-  CHECK_LAST_CONTIG(x); CHECK_LAST_CONTIG(w); CHECK_LAST_CONTIG(out);
-  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && out.dim() == 2, "dgemm: 2-D tensors");
-  const int M = x.size(0), N = w.size(0), K = w.size(1);
   TORCH_CHECK(pro >= 0 && pro <= 2, "dgemm: prologue 0|1|2");
   TORCH_CHECK(epi >= 0 && epi <= 2, "dgemm: epilogue 0|1|2");
   TORCH_CHECK(epi == 0 || pro == 0, "dgemm: epilogues 1|2 need the plain prologue");
+  // the ss_in row scale belongs to the plain prologue (the others have their own)
+  akap::DGemmArgs a = dgemm_args("dgemm", out, x, w, eps, epi,
+                                 pro == akap::PRO_PLAIN ? ss_in : std::nullopt, ss_out, aout,
+                                 ln_out);
+  const int M = a.M, N = a.N, K = a.K;
   TORCH_CHECK(x.size(1) == (pro == akap::PRO_SILU ? 2 * K : K), "dgemm: x width");
   TORCH_CHECK(out.size(0) == M && out.size(1) == (epi == akap::EPI_SILU ? N / 2 : N),
               "dgemm: out shape");
@@ -407,8 +453,6 @@ void dgemm(Tensor out, Tensor x, Tensor w, Tensor ws, int64_t pro, int64_t split
                        : akap::dgemm_epi_supported(N, epi, splitk),
               "dgemm: unsupported epilogue/N/splitk");
   TORCH_CHECK((int64_t)N * K * 2 >= (int64_t)M * 4, "dgemm: W smaller than M floats");
-  TORCH_CHECK(x.stride(0) % 8 == 0 && w.stride(0) % 8 == 0 && out.stride(0) % 4 == 0,
-              "dgemm: 16-byte aligned rows");
   if (splitk > 1) {
     const int64_t need = sk ? akap::pgemm_sk_ws_floats(M, N, (int)splitk)
                          : inlaunch ? akap::gdgemm_ws_floats(M, N, (int)splitk, tile_n, tile_m)
@@ -418,17 +462,7 @@ void dgemm(Tensor out, Tensor x, Tensor w, Tensor ws, int64_t pro, int64_t split
     TORCH_CHECK(out.stride(0) == N || inlaunch || sk,
                 "dgemm: split-K output must be dense (separate reduce pass)");
   }
-  akap::DGemmArgs a{};
-  a.ntw = akap::weight_nt_default();
-  a.stag = akap::gemm_stagger_default();
-  a.X = x.data_ptr();
-  a.W = w.data_ptr();
-  a.Y = out.data_ptr();
   a.ws = splitk > 1 ? ws.data_ptr<float>() : nullptr;
-  a.M = M; a.N = N; a.K = K;
-  a.ldx = x.stride(0); a.ldw = w.stride(0); a.ldy = out.stride(0);
-  a.eps = (float)eps;
-  a.epi = (int)epi;
   a.bn = (int)bn;
   a.ns = (int)ns;
   a.bm = (int)bm;
@@ -451,22 +485,6 @@ void dgemm(Tensor out, Tensor x, Tensor w, Tensor ws, int64_t pro, int64_t split
     a.R = r->data_ptr();
     a.Rout = rout->data_ptr();
     a.ln = ln->data_ptr();
-  }
-  if (pro == akap::PRO_PLAIN && ss_in) {
-    TORCH_CHECK(ss_in->scalar_type() == at::kFloat && ss_in->is_cuda() && ss_in->numel() >= M,
-                "dgemm: ss_in fp32 [M]");
-    a.ss_in = ss_in->data_ptr<float>();
-  }
-  if (epi == akap::EPI_RESNORM) {
-    TORCH_CHECK(ss_out && aout && ln_out, "dgemm resnorm epilogue: ss_out, aout, ln_out");
-    TORCH_CHECK(ss_out->scalar_type() == at::kFloat && ss_out->numel() >= M, "ss_out fp32 [M]");
-    CHECK_BF16(*aout); CHECK_CONTIG(*aout); CHECK_BF16(*ln_out);
-    TORCH_CHECK(aout->numel() == (int64_t)M * N && ln_out->numel() == N,
-                "dgemm resnorm: aout [M, N], ln_out [N]");
-    TORCH_CHECK(out.stride(0) == N, "dgemm resnorm: residual must be dense");
-    a.ss_out = ss_out->data_ptr<float>();
-    a.Aout = aout->data_ptr();
-    a.ln_out = ln_out->data_ptr();
   }
   const c10::DeviceGuard g(x.device());
   if (sk) {
@@ -548,37 +566,11 @@ void dequant_fp8(Tensor out, Tensor wq, Tensor scale) {
 void kgemm(Tensor out, Tensor x, Tensor w, int64_t bm, int64_t epi, double eps,
            std::optional<Tensor> ss_in, std::optional<Tensor> ss_out, std::optional<Tensor> aout,
            std::optional<Tensor> ln_out) {
-  CHECK_GPU(x); CHECK_BF16(x); CHECK_BF16(w); CHECK_BF16(out);
-  CHECK_LAST_CONTIG(x); CHECK_LAST_CONTIG(w); CHECK_LAST_CONTIG(out);
-  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && out.dim() == 2, "kgemm: 2-D tensors");
-  const int M = x.size(0), N = w.size(0), K = w.size(1);
+  TORCH_CHECK(epi == 0 || epi == 1, "kgemm: epilogue 0|1");
+  const akap::DGemmArgs a = dgemm_args("kgemm", out, x, w, eps, epi, ss_in, ss_out, aout, ln_out);
+  const int M = a.M, N = a.N, K = a.K;
   TORCH_CHECK(x.size(1) == K && out.size(0) == M && out.size(1) == N, "kgemm: shapes");
   TORCH_CHECK(akap::kgemm_supported(M, N, K, (int)bm), "kgemm: bm 16|32, N % 32, K % 256");
-  TORCH_CHECK(epi == 0 || epi == 1, "kgemm: epilogue 0|1");
-  TORCH_CHECK(x.stride(0) % 8 == 0 && w.stride(0) % 8 == 0 && out.stride(0) % 4 == 0,
-              "kgemm: aligned rows");
-  akap::DGemmArgs a{};
-  a.ntw = akap::weight_nt_default();
-  a.stag = akap::gemm_stagger_default();
-  a.X = x.data_ptr(); a.W = w.data_ptr(); a.Y = out.data_ptr();
-  a.M = M; a.N = N; a.K = K;
-  a.ldx = x.stride(0); a.ldw = w.stride(0); a.ldy = out.stride(0);
-  a.eps = (float)eps;
-  a.epi = (int)epi;
-  if (ss_in) {
-    TORCH_CHECK(ss_in->scalar_type() == at::kFloat && ss_in->numel() >= M, "ss_in fp32 [M]");
-    a.ss_in = ss_in->data_ptr<float>();
-  }
-  if (epi == 1) {
-    TORCH_CHECK(ss_out && aout && ln_out, "kgemm resnorm epilogue: ss_out, aout, ln_out");
-    TORCH_CHECK(ss_out->scalar_type() == at::kFloat && ss_out->numel() >= M, "ss_out fp32 [M]");
-    CHECK_BF16(*aout); CHECK_CONTIG(*aout); CHECK_BF16(*ln_out);
-    TORCH_CHECK(aout->numel() == (int64_t)M * N && ln_out->numel() == N && out.stride(0) == N,
-                "kgemm resnorm: aout [M, N], ln_out [N], dense residual");
-    a.ss_out = ss_out->data_ptr<float>();
-    a.Aout = aout->data_ptr();
-    a.ln_out = ln_out->data_ptr();
-  }
   const c10::DeviceGuard g(x.device());
   akap::launch_kgemm(a, (int)bm, cur_stream());
 }
