@@ -10,7 +10,7 @@ engine path.  Cache layouts (BS % 32 == 0, D = 128 on the GPU path):
 from __future__ import annotations
 
 import math
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -301,3 +301,138 @@ def pgemm(x: torch.Tensor, w: torch.Tensor, silu: bool = False,
                 y[lo:hi] = (xf[lo:hi] @ w[g].float().t()).to(x.dtype)
             lo = hi
     return silu_and_mul(y) if silu else y
+
+
+# ----------------------------------------------------------------------------- exact GEMM oracle
+# Operands for which a GEMM's fp32 accumulator is known bit for bit (tests/test_gemm_exact_*):
+# small non-zero signed integers, the weight scaled by a power of two.  Every product and every
+# partial sum is then an integer multiple of one unit below 2^24 units, so fp32 accumulation
+# is exact in ANY order (MFMA, per-wave K splits, split-K slabs, reduce passes, in-launch
+# combines) and the only roundings left are the ones the epilogue contract names
+# (csrc/kernels/gemm_common.h).
+EXACT_LIMIT = 1 << 24   # integers below this are exact in fp32
+EXACT_BF16_INT = 256    # integers below this are exact in bf16 (8 significant bits)
+
+
+class ExactOperands(NamedTuple):
+    x: torch.Tensor      # bf16 [M, K] = xi
+    w: torch.Tensor      # bf16 [N, K] = wi * unit
+    xi: torch.Tensor     # int64 image of x
+    wi: torch.Tensor     # int64 image of w (in units)
+    unit: float          # the power of two one unit of x @ w.T is worth
+
+
+def exact_vmax(K: int, resnorm_cols: int = 0) -> int:
+    """Largest operand magnitude (3, 2 or 1) that keeps an exact GEMM of depth K readable:
+    the integer result has standard deviation E[v^2] * sqrt(K) (v uniform over the non-zero
+    integers of [-vmax, vmax]); it is kept <= 128 units, so that >= 95 % of the results lie
+    within two standard deviations = 256 units and are exact in bf16 (a one-unit error is
+    visible).  resnorm_cols = N of an EPI_RESNORM case: a row's sum of N squared results
+    (mean N * std^2, relative spread sqrt(2 / N)) must also stay below 2^24 so the fp32 sum of
+    squares is exact whatever the order of the atomics: mean <= 0.6 * 2^24."""
+    for vmax in (3, 2, 1):
+        ev2 = sum(v * v for v in range(1, vmax + 1)) / vmax
+        std = ev2 * math.sqrt(K)
+        if std <= 128 and (not resnorm_cols or resnorm_cols * (std * std + 16) <= 0.6 * EXACT_LIMIT):
+            return vmax
+    raise ValueError(f"no exact operand range for K = {K}, resnorm N = {resnorm_cols}")
+
+
+def _nonzero_ints(shape, vmax: int, g: torch.Generator) -> torch.Tensor:
+    mag = torch.randint(1, vmax + 1, shape, generator=g, dtype=torch.int64)
+    sign = torch.randint(0, 2, shape, generator=g, dtype=torch.int64) * 2 - 1
+    return mag * sign
+
+
+def exact_gemm_operands(M: int, N: int, K: int, seed: int, vmax: int = 0,
+                        w_shift: int = 6) -> ExactOperands:
+    """x [M, K] and w [N, K] in bf16 with no zero entry, their int64 images and the unit
+    2^-w_shift: x = xi, w = wi * unit, entries uniform over the non-zero integers of
+    [-vmax, vmax] (vmax = 0: exact_vmax(K))."""
+    vmax = vmax or exact_vmax(K)
+    assert 1 <= vmax <= 127, "operands must stay exact in bf16"
+    g = torch.Generator().manual_seed(seed)
+    xi = _nonzero_ints((M, K), vmax, g)
+    wi = _nonzero_ints((N, K), vmax, g)
+    unit = 2.0 ** -w_shift
+    return ExactOperands(xi.to(torch.bfloat16), (wi.double() * unit).to(torch.bfloat16), xi, wi,
+                         unit)
+
+
+def exact_int_matmul(xi: torch.Tensor, wi: torch.Tensor) -> torch.Tensor:
+    """xi @ wi.T as int64.  Computed in float64 (BLAS): every partial sum is an integer far
+    below 2^53, so the double result is the integer result."""
+    return (xi.double() @ wi.double().t()).round().to(torch.int64)
+
+
+def bf16_rne(v: torch.Tensor) -> torch.Tensor:
+    """float64 -> bf16, one round-to-nearest-even (no intermediate fp32 rounding; normal
+    range only)."""
+    m, e = torch.frexp(v.double())
+    return torch.ldexp(torch.round(m * 256.0), e - 8).to(torch.bfloat16)
+
+
+def bf16_ulp_distance(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """Number of bf16 values between a and b (0 = equal bits or +-0), int64."""
+    def ordered(t):
+        i = t.contiguous().view(torch.int16).to(torch.int64)
+        return torch.where(i < 0, -(i & 0x7FFF), i)
+    return (ordered(a) - ordered(b)).abs()
+
+
+class ExactExpected(NamedTuple):
+    out: torch.Tensor                    # bf16: y, the new residual s, or the SwiGLU output
+    a: Optional[torch.Tensor] = None     # EPI_RESNORM: bf16(s * ln)
+    ss: Optional[torch.Tensor] = None    # EPI_RESNORM: fp32 exact row sums of s^2
+
+
+def _exact_bf16(vi: torch.Tensor, unit: float) -> torch.Tensor:
+    """bf16(vi * unit) by one RNE; vi * unit is exact in fp32 (|vi| < 2^24)."""
+    assert int(vi.abs().max()) < EXACT_LIMIT
+    return (vi.double() * unit).float().to(torch.bfloat16)
+
+
+def exact_gemm_expected(yi: torch.Tensor, unit: float, epi: int = 0,
+                        residual_i: Optional[torch.Tensor] = None,
+                        ln: Optional[torch.Tensor] = None,
+                        row_scale: Optional[torch.Tensor] = None,
+                        row_shift: Optional[torch.Tensor] = None) -> ExactExpected:
+    """What the epilogue contract (csrc/kernels/gemm_common.h) makes of the exact accumulator
+    yi (int64, in units; unit a power of two, or a [1, N] float64 tensor of them: per-channel
+    fp8 scales), rounding to nearest even at exactly the points it names.
+      epi 0 (EPI_STORE)    bf16(y)
+      epi 1 (EPI_RESNORM)  s = bf16(bf16(y) + residual), a = bf16(s * ln), ss = sum_n s^2;
+                           residual_i int64 in units, ln any bf16 (an 8-bit x 8-bit mantissa
+                           product is exact in fp32)
+      epi 2 (EPI_SILU)     yi = [gate | up] columns ([gate; up] weight rows -- the kernels read
+                           them in silu_interleave_perm order and write features in natural
+                           order): g = bf16(y_gate), u = bf16(y_up),
+                           out = bf16(bf16(silu(g)) * u), silu and the product in float64
+    row_scale (float64 [M], EPI_STORE only): bf16(y * row_scale) in float64 -- the ss_in row
+    scale, whose hardware rsqrt is not exact (compare within one bf16 ulp).
+    row_shift (int64 [M], any epilogue): an ss_in row scale of exactly 2^-row_shift[m].  Row m
+    is then exact in units of unit * 2^-row_shift[m] (the residual, a multiple of the unit, is
+    a multiple of that too), so every rounding of the contract stays known bit for bit."""
+    if row_scale is not None:
+        assert epi == 0 and row_shift is None
+        return ExactExpected(bf16_rne(yi.double() * unit * row_scale.double()[:, None]))
+    if row_shift is not None:
+        unit = unit * 2.0 ** -row_shift.double()[:, None]
+        if residual_i is not None:
+            residual_i = residual_i * 2 ** row_shift[:, None]
+    y = _exact_bf16(yi, unit)
+    if epi == 0:
+        return ExactExpected(y)
+    if epi == 1:
+        ti = (y.double() / unit).round().to(torch.int64) + residual_i
+        s = _exact_bf16(ti, unit)
+        si = (s.double() / unit).round().to(torch.int64)
+        a = (s.float() * ln.float()).to(torch.bfloat16)
+        ssi = (si * si).sum(-1)
+        assert int(ssi.max()) < EXACT_LIMIT, "row sum of squares not exact in fp32"
+        u2 = unit * unit
+        return ExactExpected(s, a, (ssi.double() * (u2[:, 0] if row_shift is not None else u2)).float())
+    F = yi.shape[1] // 2
+    g, u = y[:, :F].double(), y[:, F:].double()
+    sg = bf16_rne(g / (1.0 + torch.exp(-g)))
+    return ExactExpected(bf16_rne(sg.double() * u))
