@@ -35,3 +35,9 @@ def load():
                           "rebuild with python -m aws_k8s_ansible_provisioner_amd.build_ext")
     _mod = mod
     return _mod
+
+
+def contract():
+    """csrc/kernels/host_contract.h as a module: the kernels' constants, support predicates
+    and workspace sizes (CPU-built, so it works where the HIP library cannot load)."""
+    return load().contract

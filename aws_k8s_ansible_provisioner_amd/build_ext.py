@@ -66,8 +66,10 @@ def kernel_sources() -> list[str]:
 
 
 def runtime_sources() -> list[str]:
+    """The host runtime, and the kernels' HIP-free host contract its bindings expose."""
     return sorted(glob.glob(os.path.join(CSRC, "runtime", "*.cpp")) +
-                  glob.glob(os.path.join(CSRC, "runtime", "*.h")))
+                  glob.glob(os.path.join(CSRC, "runtime", "*.h")) +
+                  [os.path.join(CSRC, "kernels", "host_contract.h")])
 
 
 def kernel_tree_hash() -> str:
@@ -186,7 +188,8 @@ def build_runtime(force: bool = False, out_dir: str = PKG, sanitize: bool = Fals
     tree = runtime_tree_hash()
     cmd = ["g++", *flags, "-std=c++17", "-shared", "-fPIC", "-Wall", "-fvisibility=hidden",
            f'-DAKAP_RT_HASH="{tree}"', "-I", pybind11.get_include(), "-I",
-           sysconfig.get_paths()["include"], *srcs, "-o", out]
+           sysconfig.get_paths()["include"], "-I", os.path.join(CSRC, "kernels"), *srcs, "-o",
+           out]
     digest = _digest(runtime_sources(), " ".join(cmd))
     why = "forced" if force else ("sanitizer build" if sanitize else _stale(out, digest))
     if why:

@@ -37,8 +37,6 @@
 
 namespace akap {
 
-constexpr int DBM = 64, DBN = 64, DBK = 64;
-
 // SPL: 0 whole K, 1 fp32 partial slabs for the separate reduce pass, 2 in-launch combine of
 // the S slices (plain prologue only): fragment-native sc1 slabs + a per-tile last-arriver ticket,
 // as gdgemm.hip SPL 2 -- the reduce launch (5.0 us at Qwen3 down, M = 256) and its kernel
@@ -387,20 +385,6 @@ __global__ __launch_bounds__(256) void dgemm_reduce_kernel(DGemmArgs p) {
   }
 }
 
-bool dgemm_supported(int M, int N, int K, int splitk, int pf) {
-  if (M <= 0 || N <= 0 || K <= 0 || !dgemm_splitk_ok(splitk) || N % 4) return false;
-  if (pf != 1 && pf != 2 && pf != 4 && pf != 8) return false;
-  if (K % splitk) return false;
-  const int kps = K / splitk;
-  return kps % (DBK * pf) == 0;
-}
-
-bool dgemm_epi_supported(int N, int epi, int splitk) {
-  if (epi == EPI_SILU) return splitk == 1 && N % 32 == 0;
-  if (epi == EPI_RESNORM) return splitk == 1 || N % 256 == 0;
-  return true;
-}
-
 template <int PRO, int EPI, int SPL, int S = 1>
 static void dgemm_pf(const DGemmArgs& p, dim3 grid, int pf, hipStream_t st) {
   switch (pf) {
@@ -514,10 +498,6 @@ static void reduce_s(const DGemmArgs& p, int splitk, int blocks, hipStream_t st)
     reduce_s_idx<SCALE, EPI, int>(p, splitk, blocks, st);
   else
     reduce_s_idx<SCALE, EPI, long>(p, splitk, blocks, st);
-}
-
-bool dgemm_splitk_ok(int splitk) {
-  return splitk == 1 || splitk == 2 || splitk == 4 || splitk == 8 || splitk == 16;
 }
 
 void launch_dgemm_reduce(const DGemmArgs& p, int pro, int splitk, hipStream_t st) {

@@ -41,8 +41,6 @@
 
 namespace akap {
 
-constexpr int GBK = 64;
-
 // LDS image of a BKT-deep k-step: rows of BKT * 2 bytes in 16-B chunks, XOR-swizzled so the 16
 // lanes of a ds_read_b128 lane group (16 consecutive rows, one chunk) hit 16 distinct 16-B bank
 // positions.  BKT = 64: swz8.  BKT = 32: 4 chunks per row (four rows per 256-B bank row),
@@ -294,21 +292,6 @@ __global__ __launch_bounds__(64 * NW, OCC) void gdgemm_kernel(DGemmArgs p) {
         }
       }
     }
-}
-
-bool gdgemm_supported(int M, int N, int K, int splitk, int bn, int bm) {
-  if (bn != 64 && bn != 128) return false;
-  if (bm != 64 && !(bm == 128 && bn == 128) && bm != 256) return false;
-  if (M <= 0 || N <= 0 || K <= 0 || !dgemm_splitk_ok(splitk) || N % 4 || K % splitk) return false;
-  const int kps = K / splitk;
-  return kps % GBK == 0 && kps >= GBK;
-}
-
-long gdgemm_ws_floats(int M, int N, int splitk, int bn, int bm) {
-  const long tm = (M + bm - 1) / bm, tn = (N + bn - 1) / bn;
-  const long slabs = (long)splitk * tm * tn * bm * bn;
-  const long dense = (long)splitk * M * N;
-  return slabs > dense ? slabs : dense;
 }
 
 template <int BN, int NS, int OCC, int SPL, int S, int BM, int NW>

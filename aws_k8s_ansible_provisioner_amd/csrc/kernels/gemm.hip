@@ -16,8 +16,6 @@
 
 namespace akap {
 
-constexpr int GBM = 64, GBN = 64, GBK = 64;  // LDS tiles [64 rows][64 k] bf16, swz8 chunks
-
 template <bool SPLIT, bool CHECK, bool INREDUCE = false>
 __global__ __launch_bounds__(256) void gemm_bf16_kernel(const bf16* __restrict__ X,
                                                         const bf16* __restrict__ W,
@@ -192,13 +190,6 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
     for (int j = 0; j < 4; ++j) o[j] = f2bf(s[j]);
     *reinterpret_cast<bf16x4*>(Y + (size_t)row * ldy + col) = o;
   }
-}
-
-int gemm_splitk_choice(int M, int N, int K) {
-  const int tiles = ((M + GBM - 1) / GBM) * ((N + GBN - 1) / GBN);
-  int s = 1;
-  while (tiles * s < 256 && K / (s * 2) >= 256) s *= 2;
-  return s;
 }
 
 void launch_gemm_bf16(const void* X, const void* W, void* Y, float* ws, int M, int N, int K,

@@ -1,0 +1,226 @@
+// The host-side contract of the kernels: which shapes and variants a launch accepts, how large
+// its fp32 workspace and ticket array must be, and the layout constants both sides of a launch
+// agree on.  Plain C++17 (no HIP, no torch): kernels.h includes it for the kernels and ops.cpp,
+// and csrc/runtime/bindings.cpp exposes it to Python (`_runtime.contract`), so the bindings'
+// checks, the tuner's enumeration, the engine's workspace sizing and the tests ask one function.
+#pragma once
+
+namespace akap {
+
+// Ints per in-launch ticket counter: each counter on its own 128-B L2 line.  Atomics (and the
+// relaxed polls of a spinning combine) on one line serialise at one L2 channel -- 1024 row
+// tickets packed 32 to a line cost the sampler ~18 us at B = 16 (tools/sample_bench.py, s5c).
+constexpr int kCtrStride = 32;
+// the shared GEMM counter array (ops.gemm_counters): its size and the combine-timeout flag
+constexpr int kCtrInts = 1 << 18;
+constexpr int kCtrErr = kCtrInts - 1;
+
+// longest decode split-KV partition: 64 wave steps of 128 tokens, one cache block id per step
+constexpr int kDecodeMaxPart = 8192;
+
+enum { PRO_PLAIN = 0, PRO_ADDNORM = 1, PRO_SILU = 2 };
+enum { EPI_STORE = 0, EPI_RESNORM = 1, EPI_SILU = 2 };
+
+// ---- tile constants the predicates below share with their kernels ----
+constexpr int GBM = 64, GBN = 64, GBK = 64;  // gemm.hip tiles; gdgemm.hip k-step
+constexpr int DBM = 64, DBN = 64, DBK = 64;  // dgemm.hip
+constexpr int KBN = 32;                      // kgemm.hip: output columns per workgroup
+constexpr int KST = 256;                     // kgemm.hip: K per stage (4 waves x 64)
+constexpr int MBK = 64;                      // moe_dgemm.hip k-step
+constexpr int PG_T = 256;                    // pgemm.hip: tile rows / cols
+constexpr int PG_BK = 64;                    // pgemm.hip: K tile
+constexpr int QBK = 64;                      // qgemm.hip: k per wave step
+constexpr int QGEMM_MAX_M = 256;             // rows one qgemm launch covers
+constexpr int WBK = 64;                      // wgemm.hip k-step
+constexpr int kRouterMaxE = 16;              // moe.hip fused router: experts
+
+// ---- sampling.hip ----
+constexpr int kMaxChunks = 64;  // chunks (workgroups) per row
+constexpr int kSelWords = 16;   // per-row state of the filter passes (32-bit words)
+// per-row histogram area of the filter passes, in float2: kMaxChunks x 512 pairs (pass B
+// publishes two 256-bin sets per chunk)
+constexpr int kHistRow = kMaxChunks * 512;
+constexpr int kMaxTiles = 64;   // 2048-element tiles per chunk: chunk <= 131072 elements
+// longest row the sampler covers: kMaxChunks chunks x kMaxTiles tiles x 2048 elements
+constexpr long kSampleMaxVocab = 64L * 64 * 2048;
+
+// fp32 workspace floats of a sampler launch: partial records, selection states, per-row
+// histograms (kMaxChunks x 512 float2), the draw rows' tile masses (kMaxChunks x kMaxTiles)
+inline long sample_ws_floats(int B) {
+  return (long)B * (kMaxChunks * 8 + kSelWords + 2 * kHistRow + kMaxChunks * kMaxTiles);
+}
+
+// ---- gemm.hip ----
+// split-K factor: enough 64 x 64 tiles x slices to cover 256 CUs, each slice >= 256 of K
+inline int gemm_splitk_choice(int M, int N, int K) {
+  const int tiles = ((M + GBM - 1) / GBM) * ((N + GBN - 1) / GBN);
+  int s = 1;
+  while (tiles * s < 256 && K / (s * 2) >= 256) s *= 2;
+  return s;
+}
+
+// ---- dgemm.hip / gdgemm.hip ----
+// split-K factors with a compiled reduce (1, 2, 4, 8, 16)
+inline bool dgemm_splitk_ok(int splitk) {
+  return splitk == 1 || splitk == 2 || splitk == 4 || splitk == 8 || splitk == 16;
+}
+
+inline bool dgemm_supported(int M, int N, int K, int splitk, int pf) {
+  if (M <= 0 || N <= 0 || K <= 0 || !dgemm_splitk_ok(splitk) || N % 4) return false;
+  if (pf != 1 && pf != 2 && pf != 4 && pf != 8) return false;
+  if (K % splitk) return false;
+  const int kps = K / splitk;
+  return kps % (DBK * pf) == 0;
+}
+
+// epilogues of a launch whose K slices meet in the separate reduce pass (or that has one slice)
+inline bool dgemm_epi_supported(int N, int epi, int splitk) {
+  if (epi == EPI_SILU) return splitk == 1 && N % 32 == 0;
+  if (epi == EPI_RESNORM) return splitk == 1 || N % 256 == 0;
+  return true;
+}
+
+inline bool gdgemm_supported(int M, int N, int K, int splitk, int bn, int bm = 64) {
+  if (bn != 64 && bn != 128) return false;
+  if (bm != 64 && !(bm == 128 && bn == 128) && bm != 256) return false;
+  if (M <= 0 || N <= 0 || K <= 0 || !dgemm_splitk_ok(splitk) || N % 4 || K % splitk) return false;
+  const int kps = K / splitk;
+  return kps % GBK == 0 && kps >= GBK;
+}
+
+// fp32 workspace floats of a split-K launch that combines in the launch (tile-padded slabs)
+inline long gdgemm_ws_floats(int M, int N, int splitk, int bn, int bm = 64) {
+  if (bn <= 0 || bm <= 0) return 0;
+  const long tm = (M + bm - 1) / bm, tn = (N + bn - 1) / bn;
+  const long slabs = (long)splitk * tm * tn * bm * bn;
+  const long dense = (long)splitk * M * N;
+  return slabs > dense ? slabs : dense;
+}
+
+// ---- kgemm.hip: plain prologue, EPI_STORE / EPI_RESNORM ----
+inline bool kgemm_supported(int M, int N, int K, int bm, int epi = EPI_STORE) {
+  return M > 0 && (bm == 16 || bm == 32) && N % KBN == 0 && K >= KST && K % KST == 0 &&
+         (epi == EPI_STORE || epi == EPI_RESNORM);
+}
+
+// ---- pgemm.hip ----
+// ldx: row stride of X in elements.  The DMA addresses X and one group's W through buffer
+// descriptors with 32-bit offsets, so both stay below 2 GiB.
+inline bool pgemm_supported(int M, int N, int K, long ldx) {
+  return M > 0 && N > 0 && N % PG_T == 0 && K >= PG_BK && K % PG_BK == 0 &&
+         (long)M * ldx * 2 < (1L << 31) && (long)N * K * 2 < (1L << 31);
+}
+
+// the decode split-K form: grid = tiles * splits <= the CU count (all slices resident), two
+// tickets per tile below the error word
+inline bool pgemm_sk_supported(int M, int N, int K, int splits, int cus) {
+  const int nk = K / PG_BK;
+  const long grid = (long)((M + PG_T - 1) / PG_T) * (N / PG_T) * splits;
+  return M > 0 && N % PG_T == 0 && K % PG_BK == 0 && splits >= 1 && splits <= 32 &&
+         nk >= splits && grid <= cus &&
+         (N / PG_T) * ((M + PG_T - 1) / PG_T) * 2 * kCtrStride < kCtrErr;
+}
+
+inline long pgemm_sk_ws_floats(int M, int N, int splits) {
+  if (splits <= 1) return 0;
+  return (long)((M + PG_T - 1) / PG_T) * (N / PG_T) * splits * PG_T * PG_T;
+}
+
+// ---- wgemm.hip ----
+inline bool wgemm_supported(int M, int N, int K, int ldx, int ldw, int ldy) {
+  return M > 0 && N > 0 && K >= WBK && K % WBK == 0 && ldx % 8 == 0 && ldw % 8 == 0 &&
+         ldy % 8 == 0;
+}
+
+// ---- qgemm.hip ----
+struct QGemmGeom {
+  int bm, bn;  // output tile of one 4-wave workgroup (K is split over its waves)
+  int grid;
+};
+
+// The one place the geometry is chosen.  Rows: the smallest tile that holds M (64-row tiles
+// above 32 rows).  Columns: 64 when that still gives every CU a workgroup ("wide N": half the
+// X re-reads per weight byte), else 32 ("narrow N": more workgroups for the o / down
+// projections), and 16 for the 16-row tile when 32 columns would leave half the CUs or more
+// without a workgroup (N <= 4,096 at M <= 16: a pure weight stream, so the number of
+// workgroups with DMAs in flight is what bounds it).
+inline QGemmGeom qgemm_geometry(int M, int N, int K) {
+  (void)K;
+  constexpr int kCus = 256;
+  QGemmGeom g;
+  g.bm = M <= 16 ? 16 : (M <= 32 ? 32 : 64);
+  const int tiles_m = (M + g.bm - 1) / g.bm;
+  if (((N + 63) / 64) * tiles_m >= kCus) g.bn = 64;
+  else if (g.bm == 16 && (N + 31) / 32 <= kCus / 2) g.bn = 16;
+  else g.bn = 32;
+  g.grid = tiles_m * ((N + g.bn - 1) / g.bn);
+  return g;
+}
+
+inline bool qgemm_supported(int M, int N, int K, int ldx, int ldy) {
+  return M > 0 && M <= QGEMM_MAX_M && N > 0 && N % 8 == 0 && K >= QBK && K % QBK == 0 &&
+         ldx % 8 == 0 && ldy % 8 == 0;
+}
+
+// ---- moe_dgemm.hip / moe.hip ----
+inline bool moe_dgemm_supported(int N, int K, int pf, int silu, int splitk) {
+  if (pf != 1 && pf != 2 && pf != 4) return false;
+  if (splitk < 1 || K % splitk || (K / splitk) % (MBK * pf)) return false;
+  if (silu && splitk > 1) return false;
+  return silu ? N % 32 == 0 : N % 8 == 0;
+}
+
+inline bool moe_router_topk_supported(int E, int d) {
+  return E >= 1 && E <= kRouterMaxE && d % 8 == 0;
+}
+
+// ---- the dgemm op's launch contract (torch.ops.akap.dgemm: dgemm.hip, gdgemm.hip and the
+// pgemm.hip split-K body behind one binding) ----
+enum { DG_RING = 0, DG_LDS = 1, DG_PGEMM_SK = 2 };
+struct DGemmContract {
+  bool supported;    // the binding accepts the launch
+  int family;        // DG_RING (bn = 0) | DG_LDS (bn 64 | 128) | DG_PGEMM_SK (bn = 256)
+  bool inlaunch;     // the K slices are combined through tile tickets, no separate reduce pass
+  long ws_floats;    // fp32 workspace the launch needs (0: none)
+  long ticket_ints;  // zeroed int32 tickets it needs (0: none)
+};
+
+// inlaunch: the caller asks for (offers tickets for) the in-launch combine.  Every LDS-DMA
+// variant takes it; the register ring only with the plain prologue and 2 | 4 | 8 slices, and
+// otherwise runs its separate reduce pass; the 256 x 256 body always combines in the launch.
+// cus: the device's compute units (the 256 x 256 body needs every slice resident).  ns (the
+// LDS ring depth) is any value: the launcher maps it to a compiled depth.
+inline DGemmContract dgemm_contract(int M, int N, int K, int pro, int epi, int splitk, int pf,
+                                    int bn, int ns, int bm, bool inlaunch, int cus) {
+  (void)ns;
+  DGemmContract c{};
+  const bool sk = bn == 256;
+  c.family = sk ? DG_PGEMM_SK : bn > 0 ? DG_LDS : DG_RING;
+  c.inlaunch = splitk > 1 && (sk || (inlaunch && (bn > 0 || (pro == PRO_PLAIN &&
+                                                             (splitk == 2 || splitk == 4 ||
+                                                              splitk == 8)))));
+  c.supported =
+      pro >= PRO_PLAIN && pro <= PRO_SILU && epi >= EPI_STORE && epi <= EPI_SILU &&
+      (epi == EPI_STORE || pro == PRO_PLAIN) &&  // epilogues need the plain prologue,
+      (bn == 0 || pro == PRO_PLAIN) &&           // and so do the LDS-DMA variants
+      (bm == 64 || bn > 0) &&                    // taller tiles are LDS-DMA variants
+      (sk ? pgemm_sk_supported(M, N, K, splitk, cus)
+          : bn > 0 ? gdgemm_supported(M, N, K, splitk, bn, bm)
+                   : dgemm_supported(M, N, K, splitk, pf)) &&
+      (c.inlaunch ? (epi != EPI_SILU || N % 32 == 0) : dgemm_epi_supported(N, epi, splitk)) &&
+      (long)N * K * 2 >= (long)M * 4;  // W at least M floats
+  // the sizes follow from M, N and the variant alone (any K, any epilogue)
+  const int tile_n = bn > 0 ? bn : DBN, tile_m = bn > 0 ? bm : DBM;
+  if (splitk > 1 && tile_m > 0) {
+    c.ws_floats = sk ? pgemm_sk_ws_floats(M, N, splitk)
+                  : c.inlaunch ? gdgemm_ws_floats(M, N, splitk, tile_n, tile_m)
+                               : (long)splitk * M * N + (pro == PRO_ADDNORM ? (long)splitk * M : 0);
+    if (c.inlaunch)
+      c.ticket_ints = sk ? (long)kCtrInts
+                         : (long)((M + tile_m - 1) / tile_m) * ((N + tile_n - 1) / tile_n) *
+                               kCtrStride;
+  }
+  return c;
+}
+
+}  // namespace akap

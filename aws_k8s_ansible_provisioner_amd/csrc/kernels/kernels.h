@@ -5,18 +5,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// the constants, support predicates and workspace sizes of these launchers (HIP-free)
+#include "host_contract.h"
+
 namespace akap {
-
-// Ints per in-launch ticket counter: each counter on its own 128-B L2 line.  Atomics (and the
-// relaxed polls of a spinning combine) on one line serialise at one L2 channel -- 1024 row
-// tickets packed 32 to a line cost the sampler ~18 us at B = 16 (tools/sample_bench.py, s5c).
-constexpr int kCtrStride = 32;
-// the shared GEMM counter array (ops.gemm_counters): its size and the combine-timeout flag
-constexpr int kCtrInts = 1 << 18;
-constexpr int kCtrErr = kCtrInts - 1;
-
-
-constexpr int kDecodeMaxPart = 8192;
 
 // ---- norm.hip ----
 void launch_rmsnorm(void* out, const void* x, const void* w, int rows, int d, int x_stride,
@@ -93,7 +85,6 @@ void launch_paged_attn_prefill(const AttnParams& p, int num_tiles, int tile_rows
 void launch_paged_attn_decode(const AttnParams& p, int num_seqs, hipStream_t s);
 
 // ---- gemm.hip ----
-int gemm_splitk_choice(int M, int N, int K);
 // counters: zero-initialised int32 per-tile tickets (>= tiles) -> split-K partials are
 // combined inside the launch by the last-arriving slice; nullptr -> separate reduce pass
 void launch_gemm_bf16(const void* X, const void* W, void* Y, float* ws, int M, int N, int K,
@@ -104,8 +95,6 @@ void launch_gemm_bf16(const void* X, const void* W, void* Y, float* ws, int M, i
 // Fused decode GEMM: A-operand prologue (PRO_*) folded into the MFMA GEMM's staging, and an
 // epilogue (EPI_*) doing a decode layer's residual add + next-norm elementwise half, or SwiGLU.
 // Split-K partials (+ per-row sums of squares) are reduced by a second pass with the same epilogue.
-enum { PRO_PLAIN = 0, PRO_ADDNORM = 1, PRO_SILU = 2 };
-enum { EPI_STORE = 0, EPI_RESNORM = 1, EPI_SILU = 2 };
 struct DGemmArgs {
   // bf16 tensors (void* so this header stays free of device types)
   const void* X;     // A source: [M, K] (PLAIN/ADDNORM) or [M, 2K] = [gate | up] (SILU)
@@ -138,20 +127,12 @@ int gemm_stagger_default();
 __device__ __forceinline__ int gemm_stagger0(int stag, int tm, int tn, int nk) {
   return stag ? (tn + 3 * tm) % nk : 0;
 }
-bool dgemm_supported(int M, int N, int K, int splitk, int pf);
-// split-K factors with a compiled reduce (1, 2, 4, 8, 16)
-bool dgemm_splitk_ok(int splitk);
-bool dgemm_epi_supported(int N, int epi, int splitk);
 void launch_dgemm(const DGemmArgs& a, int pro, int splitk, int pf, hipStream_t st);
 void launch_dgemm_reduce(const DGemmArgs& p, int pro, int splitk, hipStream_t st);
 // gdgemm.hip: the same plain-prologue GEMM + epilogues with operands staged by global_load_lds
-bool gdgemm_supported(int M, int N, int K, int splitk, int bn, int bm = 64);
-// fp32 workspace floats a gdgemm split-K launch needs (tile-padded slabs)
-long gdgemm_ws_floats(int M, int N, int splitk, int bn, int bm = 64);
 void launch_gdgemm(const DGemmArgs& p, int splitk, hipStream_t st);
 // kgemm.hip: BM (16 | 32) x 32 output tiles, K split over the workgroup's 4 waves (no global
 // partials, no reduce launch); plain prologue, EPI_STORE / EPI_RESNORM, optional ss_in
-bool kgemm_supported(int M, int N, int K, int bm);
 void launch_kgemm(const DGemmArgs& p, int bm, hipStream_t st);
 
 // ---- pgemm.hip: prefill / large-M GEMM Y = X . W^T, 256 x 256 tiles, optional expert groups
@@ -165,15 +146,12 @@ struct PGemmArgs {
   int stagger;      // unit body: workgroups start their K loops at decorrelated offsets
   int gm;           // raster: M tiles per block of the tile map (0 = 8)
 };
-bool pgemm_supported(int M, int N, int K);
 void launch_pgemm(const PGemmArgs& p, int epi, hipStream_t st);
 // decode-sized M: the same 256 x 256 body with K split over `splits` workgroups per tile and
 // the slices combined in the launch (DGemmArgs epilogues: store | RESNORM | SILU, ss_in row
 // scale).  Needs grid = tiles * splits <= the CU count (all slices resident); ws fp32
 // pgemm_sk_ws_floats(); counters: 2 zeroed ints per tile (re-armed by the kernel), the error
 // word at counters[65535].
-bool pgemm_sk_supported(int M, int N, int K, int splits, int cus);
-long pgemm_sk_ws_floats(int M, int N, int splits);
 void launch_pgemm_sk(const DGemmArgs& p, int splits, hipStream_t st);
 
 // ---- wgemm.hip: wide-row weight-streaming GEMM (LM head) Y[M,N] = X[M,K] . W[N,K]^T ----
@@ -183,7 +161,6 @@ struct WGemmArgs {
   void* Y;        // bf16 [M, N] (row stride ldy)
   int M, N, K, ldx, ldw, ldy;
 };
-bool wgemm_supported(int M, int N, int K, int ldx, int ldw, int ldy);
 void launch_wgemm(const WGemmArgs& p, hipStream_t st);
 
 // ---- qgemm.hip: FP8-weight (e4m3fn bytes + per-channel fp32 scale) decode GEMM, M <= 256 ----
@@ -196,13 +173,7 @@ struct QGemmArgs {
   void* Y;             // bf16 [M, N] (row stride ldy)
   int M, N, K, ldx, ldy;
 };
-struct QGemmGeom {
-  int bm, bn;  // output tile of one 4-wave workgroup (K is split over its waves)
-  int grid;
-};
-// pure: the tile geometry launch_qgemm uses for a shape
-QGemmGeom qgemm_geometry(int M, int N, int K);
-bool qgemm_supported(int M, int N, int K, int ldx, int ldy);
+// launches the tile geometry qgemm_geometry() picks
 void launch_qgemm(const QGemmArgs& p, hipStream_t st);
 // out[n, k] = bf16(float(q[n, k]) * scale[n]); q uint8 [N, K], out bf16 [N, K], K % 16 == 0
 void launch_dequant_fp8(const void* q, const float* scale, void* out, long N, int K,
@@ -222,12 +193,9 @@ struct SampleParams {
   float* out_logprobs;       // [B] log-prob of the sampled token (may be null)
   int greedy_logprobs;       // also compute log-probs for greedy rows (one extra pass)
 };
-// grid (sample_chunks(B, V) chunks, B rows); ws >= B * kMaxChunks * 32 bytes of partials,
-// tickets[B] int32 zeroed once (each row's last chunk re-arms its ticket)
+// grid (sample_chunks(B, V) chunks, B rows); ws >= sample_ws_floats(B) floats, tickets: one
+// per row, kCtrStride ints apart, zeroed once (each row's last chunk re-arms its ticket)
 int sample_chunks(int B, int V, int wgs = 512);
-// longest row the sampler covers: kMaxChunks chunks x kMaxTiles tiles x kTile elements
-constexpr long kSampleMaxVocab = 64L * 64 * 2048;
-long sample_ws_floats(int B);  // partial records + filter-pass states and histograms
 // filtered = 0: the caller guarantees no row has top-k / top-p (their passes are not launched)
 void launch_sample(const SampleParams& p, int B, void* ws, int* tickets, int filtered,
                    hipStream_t s);
@@ -244,7 +212,6 @@ void launch_argmax(const void* logits, int ld, int V, int is_bf16, int64_t* out,
 // ---- moe_dgemm.hip ----
 // Grouped expert GEMM for MoE decode: 32|64-row x 128-col tiles, k-pipelined, optional
 // activation-row gather and SwiGLU epilogue over gate/up-interleaved weight rows.
-bool moe_dgemm_supported(int N, int K, int pf, int silu, int splitk);
 void launch_moe_dgemm(const void* A, const void* W, void* Y, const int32_t* sorted_ids,
                       const int32_t* tile_expert, int max_tiles, int n_flat, int topk, int N,
                       int K, int lda, int ldy, int gather, int silu, int pf, int bm, int splitk,
@@ -257,7 +224,6 @@ void launch_moe_combine_split(const float* P, const float* wts, const int32_t* i
 void launch_moe_topk_softmax(const void* logits, int ld, int E, int K, float* topk_w,
                              int32_t* topk_ids, int T, int renormalize, hipStream_t s);
 // router GEMM (h [T, d] . W[E, d]^T, bf16-rounded logits) + softmax + top-k, E <= 16
-bool moe_router_topk_supported(int E, int d);
 void launch_moe_router_topk(const void* h, int ldh, const void* W, int d, int E, int K,
                             float* topk_w, int32_t* topk_ids, int T, int renormalize,
                             hipStream_t s);

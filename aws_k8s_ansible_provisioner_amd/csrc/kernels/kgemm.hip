@@ -24,9 +24,6 @@
 
 namespace akap {
 
-constexpr int KBN = 32;    // output columns per workgroup
-constexpr int KST = 256;   // K per stage (4 waves x 64)
-
 __device__ __forceinline__ int kswz(int row, int chunk) { return row * 32 + (chunk ^ (row & 15)); }
 
 // KNS = 4 ring slots: 3 stages (96 KB) in flight (a 5-slot ring lost 0.5 % end to end and was
@@ -168,10 +165,6 @@ __global__ __launch_bounds__(256, 1) void kgemm_kernel(DGemmArgs p) {
     *reinterpret_cast<bf16x4*>(static_cast<bf16*>(p.Aout) + (size_t)erow * p.N + n0 + ec) = a;
     if ((tid & 7) == 0) atomicAdd(p.ss_out + erow, q2);
   }
-}
-
-bool kgemm_supported(int M, int N, int K, int bm) {
-  return M > 0 && (bm == 16 || bm == 32) && N % KBN == 0 && K >= KST && K % KST == 0;
 }
 
 void launch_kgemm(const DGemmArgs& p, int bm, hipStream_t st) {

@@ -65,8 +65,6 @@ __global__ __launch_bounds__(256) void moe_topk_softmax_kernel(const T* __restri
 // across the workgroup, and the logits are rounded to bf16 like the separate F.linear's
 // output before the softmax.  Replaces a hipBLASLt launch (M x 8 output: 13.5 us at M = 128)
 // plus the top-k launch (profiles/r2_mixtral_bench_kernel_stats.md).
-constexpr int kRouterMaxE = 16;
-
 __global__ __launch_bounds__(256) void moe_router_topk_kernel(const bf16* __restrict__ h, int ldh,
                                                               const bf16* __restrict__ W, int d,
                                                               int E, int K,
@@ -108,8 +106,6 @@ __global__ __launch_bounds__(256) void moe_router_topk_kernel(const bf16* __rest
     topk_softmax_row([&](int e) { return logit[e]; }, E, K, topk_w + (size_t)t * K,
                      topk_ids + (size_t)t * K, renorm);
 }
-
-bool moe_router_topk_supported(int E, int d) { return E >= 1 && E <= kRouterMaxE && d % 8 == 0; }
 
 void launch_moe_router_topk(const void* h, int ldh, const void* W, int d, int E, int K,
                             float* topk_w, int32_t* topk_ids, int T, int renormalize,

@@ -21,7 +21,7 @@
 
 namespace akap {
 
-constexpr int MBN = 128, MBK = 64;
+constexpr int MBN = 128;
 
 // BM = rows per tile (32 or 64): 4 waves as WM (= BM/32) x WN (= 4/WM), each owning a
 // 32-row x (128/WN)-col sub-tile = 2 x JN 16x16 MFMA tiles.
@@ -163,13 +163,6 @@ __global__ __launch_bounds__(256, 2) void moe_dgemm_kernel(const bf16* __restric
         }
       }
     }
-}
-
-bool moe_dgemm_supported(int N, int K, int pf, int silu, int splitk) {
-  if (pf != 1 && pf != 2 && pf != 4) return false;
-  if (splitk < 1 || K % splitk || (K / splitk) % (MBK * pf)) return false;
-  if (silu && splitk > 1) return false;
-  return silu ? N % 32 == 0 : N % 8 == 0;
 }
 
 // out[t] = sum_k w[t,k] * sum_z P[z, inv[t*K+k]]  (fp32 partial slices of the down GEMM)

@@ -59,8 +59,6 @@
 
 namespace akap {
 
-constexpr int PG_T = 256;        // tile rows / cols
-constexpr int PG_BK = 64;        // K tile
 constexpr int PG_THREADS = 512;  // 8 waves
 constexpr int PG_BUF = 2 * PG_T * 8;  // 16-B units per LDS buffer (A 256 rows + W 256 rows)
 
@@ -837,19 +835,6 @@ __global__ __launch_bounds__(WAVES * 64, 1) void pgemm_sk_kernel(DGemmArgs p, in
   }
 }
 
-bool pgemm_sk_supported(int M, int N, int K, int splits, int cus) {
-  const int nk = K / PG_BK;
-  const long grid = (long)((M + PG_T - 1) / PG_T) * (N / PG_T) * splits;
-  return M > 0 && N % PG_T == 0 && K % PG_BK == 0 && splits >= 1 && splits <= 32 &&
-         nk >= splits && grid <= cus &&
-         (N / PG_T) * ((M + PG_T - 1) / PG_T) * 2 * kCtrStride < kCtrErr;
-}
-
-long pgemm_sk_ws_floats(int M, int N, int splits) {
-  if (splits <= 1) return 0;
-  return (long)((M + PG_T - 1) / PG_T) * (N / PG_T) * splits * PG_T * PG_T;
-}
-
 // Wave form of the 256 x 256 body: AKAP_PGEMM_WAVES = 8 (2 x 4 waves of 128 x 64) or 4 (2 x 2
 // waves of 128 x 128), read once per process.
 // K-loop issue schedule: AKAP_PGEMM_SCHED = 1 (phase pipeline, half-tiles requested 1.0-1.25
@@ -894,10 +879,6 @@ void launch_pgemm_sk(const DGemmArgs& p, int splits, hipStream_t st) {
     if (pgemm_sched() == 2) launch_pgemm_sk_w<8, 2>(p, splits, st);
     else launch_pgemm_sk_w<8, 1>(p, splits, st);
   }
-}
-
-bool pgemm_supported(int M, int N, int K) {
-  return M > 0 && N > 0 && N % PG_T == 0 && K >= PG_BK && K % PG_BK == 0;
 }
 
 template <int WAVES, int SCHED>

@@ -29,8 +29,6 @@
 
 namespace akap {
 
-constexpr int QBK = 64;  // k per wave step
-
 // X rows (128 B) use swz8.  W rows of 64 B: chunk c stored at c ^ g((row >> 2) & 3),
 // g = {0, 2, 3, 1} (wgemm.hip ww_swz)
 __device__ __forceinline__ int qswz_g(int row) { return (0x1320 >> (4 * ((row >> 2) & 3))) & 3; }
@@ -168,30 +166,6 @@ __global__ __launch_bounds__(256, 1) void qgemm_kernel(QGemmArgs p) {
     }
     *reinterpret_cast<bf16x8*>(Y + (size_t)row * p.ldy + col) = o;
   }
-}
-
-// The one place the geometry is chosen.  Rows: the smallest tile that holds M (64-row tiles
-// above 32 rows).  Columns: 64 when that still gives every CU a workgroup ("wide N": half the
-// X re-reads per weight byte), else 32 ("narrow N": more workgroups for the o / down
-// projections), and 16 for the 16-row tile when 32 columns would leave half the CUs or more
-// without a workgroup (N <= 4,096 at M <= 16: a pure weight stream, so the number of
-// workgroups with DMAs in flight is what bounds it).
-QGemmGeom qgemm_geometry(int M, int N, int K) {
-  (void)K;
-  constexpr int kCus = 256;
-  QGemmGeom g;
-  g.bm = M <= 16 ? 16 : (M <= 32 ? 32 : 64);
-  const int tiles_m = (M + g.bm - 1) / g.bm;
-  if (((N + 63) / 64) * tiles_m >= kCus) g.bn = 64;
-  else if (g.bm == 16 && (N + 31) / 32 <= kCus / 2) g.bn = 16;
-  else g.bn = 32;
-  g.grid = tiles_m * ((N + g.bn - 1) / g.bn);
-  return g;
-}
-
-bool qgemm_supported(int M, int N, int K, int ldx, int ldy) {
-  return M > 0 && M <= 256 && N > 0 && N % 8 == 0 && K >= QBK && K % QBK == 0 && ldx % 8 == 0 &&
-         ldy % 8 == 0;
 }
 
 void launch_qgemm(const QGemmArgs& p, hipStream_t st) {

@@ -92,17 +92,11 @@ __device__ __forceinline__ ArgBest block_argmax(ArgBest b, float* sv, int* si) {
 //    for top-k, by probability MASS for top-p on the top-k renormalised distribution -- then
 //    the Gumbel draw over the survivors (details above sample_pass_kernel).
 constexpr int kChunkThreads = 256;
-constexpr int kMaxChunks = 64;
 constexpr int kSc1 = 16;  // buffer op cache bits: sc1 (write-through stores, L1-bypass loads)
-constexpr int kSelWords = 16;  // per-row state of the filter passes (32-bit words)
-// per-row histogram area of the filter passes, in float2: kMaxChunks x 512 pairs (pass B
-// publishes two 256-bin sets per chunk)
-constexpr int kHistRow = kMaxChunks * 512;
 // draw rows (T > 0, no filter): a chunk is cut into tiles of 2048 consecutive elements (one
 // 16-byte vector per thread); the chunk kernel publishes every tile's mass, so the row's last
 // chunk rescans ONE tile for the token whatever the chunk size
 constexpr int kTile = kChunkThreads * 8;
-constexpr int kMaxTiles = 64;  // chunk <= 131072 elements
 static_assert((long)kMaxChunks * kMaxTiles * kTile == kSampleMaxVocab, "kernels.h bound");
 
 struct SampPart {  // one chunk's partial record (32 B = two 16-B vectors)
@@ -994,12 +988,6 @@ int sample_chunks(int B, int V, int wgs) {
   S = min(S, max(1, V / 2048));
   S = max(S, need);
   return max(1, min(S, kMaxChunks));
-}
-
-long sample_ws_floats(int B) {
-  // partial records, selection states, per-row histograms (kMaxChunks x 512 float2), the
-  // draw rows' tile masses (kMaxChunks x kMaxTiles)
-  return (long)B * (kMaxChunks * 8 + kSelWords + 2 * kHistRow + kMaxChunks * kMaxTiles);
 }
 
 // Chunks per row of the filter passes: each pass has a fixed cost per workgroup (publish,

@@ -26,7 +26,6 @@
 
 namespace akap {
 
-constexpr int WBK = 64;
 constexpr int WNS = 3;
 
 template <int WM>
@@ -279,11 +278,6 @@ static int wgemm_wide() {
 }
 
 int wgemm_rows(int M) { return M <= 64 ? 1 : (M <= 128 ? 2 : 4); }
-
-bool wgemm_supported(int M, int N, int K, int ldx, int ldw, int ldy) {
-  return M > 0 && N > 0 && K >= WBK && K % WBK == 0 && ldx % 8 == 0 && ldw % 8 == 0 &&
-         ldy % 8 == 0;
-}
 
 void launch_wgemm(const WGemmArgs& p, hipStream_t st) {
   if (p.M == 0 || p.N == 0) return;

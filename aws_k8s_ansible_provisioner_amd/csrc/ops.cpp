@@ -423,7 +423,6 @@ void dgemm(Tensor out, Tensor x, Tensor w, Tensor ws, int64_t pro, int64_t split
            std::optional<Tensor> counters, int64_t bm) {
   TORCH_CHECK(pro >= 0 && pro <= 2, "dgemm: prologue 0|1|2");
   TORCH_CHECK(epi >= 0 && epi <= 2, "dgemm: epilogue 0|1|2");
-  TORCH_CHECK(epi == 0 || pro == 0, "dgemm: epilogues 1|2 need the plain prologue");
   // the ss_in row scale belongs to the plain prologue (the others have their own)
   akap::DGemmArgs a = dgemm_args("dgemm", out, x, w, eps, epi,
                                  pro == akap::PRO_PLAIN ? ss_in : std::nullopt, ss_out, aout,
@@ -432,46 +431,27 @@ void dgemm(Tensor out, Tensor x, Tensor w, Tensor ws, int64_t pro, int64_t split
   TORCH_CHECK(x.size(1) == (pro == akap::PRO_SILU ? 2 * K : K), "dgemm: x width");
   TORCH_CHECK(out.size(0) == M && out.size(1) == (epi == akap::EPI_SILU ? N / 2 : N),
               "dgemm: out shape");
-  TORCH_CHECK(bn == 0 || pro == akap::PRO_PLAIN, "dgemm: the LDS-DMA variant has the plain prologue");
-  TORCH_CHECK(bm == 64 || bn > 0, "dgemm: 128-row tiles are an LDS-DMA (bn > 0) variant");
-  // bn == 256: the 256 x 256 pgemm body with an in-launch distributed split-K combine
-  // (pgemm.hip pgemm_sk_kernel); the grid must fit the CUs (every slice resident)
-  const bool sk = bn == 256;
-  TORCH_CHECK(sk ? akap::pgemm_sk_supported(M, N, K, (int)splitk, device_cus(x.device().index()))
-                 : bn > 0 ? akap::gdgemm_supported(M, N, K, splitk, bn, bm)
-                          : akap::dgemm_supported(M, N, K, splitk, pf),
-              "dgemm: unsupported M/N/K/splitk/pf/bn");
-  TORCH_CHECK(!sk || splitk == 1 || counters.has_value(),
-              "dgemm bn=256: split-K needs the counters (2 per tile)");
-  // in-launch split-K combine: the LDS-DMA variants (bn > 0) and, with the plain prologue and
-  // 2 | 4 | 8 slices, the register-ring kernel (64 x 64 tiles)
-  const bool inlaunch = counters.has_value() && splitk > 1 &&
-                        (bn > 0 || (pro == akap::PRO_PLAIN && (splitk == 2 || splitk == 4 ||
-                                                               splitk == 8)));
-  const int tile_n = bn > 0 ? (int)bn : 64, tile_m = bn > 0 ? (int)bm : 64;
-  TORCH_CHECK(inlaunch ? (epi != akap::EPI_SILU || N % 32 == 0)
-                       : akap::dgemm_epi_supported(N, epi, splitk),
-              "dgemm: unsupported epilogue/N/splitk");
-  TORCH_CHECK((int64_t)N * K * 2 >= (int64_t)M * 4, "dgemm: W smaller than M floats");
+  // what the launch accepts and needs: host_contract.h (offering counters asks for the
+  // in-launch combine)
+  const akap::DGemmContract c =
+      akap::dgemm_contract(M, N, K, (int)pro, (int)epi, (int)splitk, (int)pf, (int)bn, (int)ns,
+                           (int)bm, counters.has_value(), device_cus(x.device().index()));
+  TORCH_CHECK(c.supported, "dgemm: unsupported M/N/K/pro/epi/splitk/pf/bn/bm");
   if (splitk > 1) {
-    const int64_t need = sk ? akap::pgemm_sk_ws_floats(M, N, (int)splitk)
-                         : inlaunch ? akap::gdgemm_ws_floats(M, N, (int)splitk, tile_n, tile_m)
-                                    : splitk * M * N + (pro == akap::PRO_ADDNORM ? splitk * M : 0);
-    TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.numel() >= need,
+    TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.numel() >= c.ws_floats,
                 "dgemm: fp32 workspace of splitk*M*N (+ splitk*M for the norm)");
-    TORCH_CHECK(out.stride(0) == N || inlaunch || sk,
+    TORCH_CHECK(out.stride(0) == N || c.inlaunch,
                 "dgemm: split-K output must be dense (separate reduce pass)");
   }
   a.ws = splitk > 1 ? ws.data_ptr<float>() : nullptr;
   a.bn = (int)bn;
   a.ns = (int)ns;
   a.bm = (int)bm;
-  if (inlaunch || (sk && counters && splitk > 1)) {
+  if (c.ticket_ints > 0) {
     // in-launch split-K combine: one zeroed int32 ticket per output tile
+    TORCH_CHECK(counters.has_value(), "dgemm bn=256: split-K needs the counters (2 per tile)");
     TORCH_CHECK(counters->scalar_type() == at::kInt && counters->is_cuda() &&
-                    counters->numel() >= (sk ? (int64_t)akap::kCtrInts
-                                             : (int64_t)((M + tile_m - 1) / tile_m) *
-                                                   ((N + tile_n - 1) / tile_n) * akap::kCtrStride),
+                    counters->numel() >= c.ticket_ints,
                 "dgemm: counters int32, one L2 line per output tile (bn=256: the kCtrInts array)");
     a.counters = counters->data_ptr<int>();
   }
@@ -487,7 +467,7 @@ void dgemm(Tensor out, Tensor x, Tensor w, Tensor ws, int64_t pro, int64_t split
     a.ln = ln->data_ptr();
   }
   const c10::DeviceGuard g(x.device());
-  if (sk) {
+  if (c.family == akap::DG_PGEMM_SK) {
     akap::launch_pgemm_sk(a, (int)splitk, cur_stream());
     return;
   }
@@ -570,13 +550,9 @@ void kgemm(Tensor out, Tensor x, Tensor w, int64_t bm, int64_t epi, double eps,
   const akap::DGemmArgs a = dgemm_args("kgemm", out, x, w, eps, epi, ss_in, ss_out, aout, ln_out);
   const int M = a.M, N = a.N, K = a.K;
   TORCH_CHECK(x.size(1) == K && out.size(0) == M && out.size(1) == N, "kgemm: shapes");
-  TORCH_CHECK(akap::kgemm_supported(M, N, K, (int)bm), "kgemm: bm 16|32, N % 32, K % 256");
+  TORCH_CHECK(akap::kgemm_supported(M, N, K, (int)bm, (int)epi), "kgemm: bm 16|32, N % 32, K % 256");
   const c10::DeviceGuard g(x.device());
   akap::launch_kgemm(a, (int)bm, cur_stream());
-}
-
-bool dgemm_ok(int64_t M, int64_t N, int64_t K, int64_t splitk, int64_t pf) {
-  return akap::dgemm_supported(M, N, K, splitk, pf);
 }
 
 void sample(Tensor logits, Tensor temperature, Tensor top_k, Tensor top_p, Tensor seeds,
@@ -874,7 +850,8 @@ void pgemm(Tensor out, Tensor x, Tensor w, int64_t epi, std::optional<Tensor> of
   a.K = x.size(1);
   a.N = w.size(-2);
   TORCH_CHECK(w.size(-1) == a.K, "w [.., N, K] must match x [M, K]");
-  TORCH_CHECK(akap::pgemm_supported(a.M, a.N, a.K), "pgemm: N % 256 == 0 and K % 64 == 0 needed");
+  TORCH_CHECK(akap::pgemm_supported(a.M, a.N, a.K, x.stride(0)),
+              "pgemm: N % 256 == 0 and K % 64 == 0 needed, X and each weight matrix below 2 GiB");
   TORCH_CHECK(out.size(0) == a.M && out.size(1) == (epi == akap::EPI_SILU ? a.N / 2 : a.N),
               "out shape");
   if (offs) {
@@ -892,10 +869,6 @@ void pgemm(Tensor out, Tensor x, Tensor w, int64_t epi, std::optional<Tensor> of
   a.ldx = x.stride(0);
   a.ldy = out.stride(0);
   TORCH_CHECK(a.ldx % 8 == 0 && a.ldy % 4 == 0, "row strides must keep 16-B / 8-B alignment");
-  // the DMA addresses X and one group's W through buffer descriptors with 32-bit offsets
-  TORCH_CHECK((int64_t)a.M * a.ldx * 2 < (int64_t(1) << 31) &&
-                  (int64_t)a.N * a.K * 2 < (int64_t(1) << 31),
-              "pgemm: X and each weight matrix must stay below 2 GiB");
   const c10::DeviceGuard g(x.device());
   akap::launch_pgemm(a, (int)epi, cur_stream());
 }
@@ -1340,7 +1313,6 @@ TORCH_LIBRARY(akap, m) {
   m.def("pgemm(Tensor(a!) out, Tensor x, Tensor w, int epi=0, Tensor? offs=None) -> ()");
   m.def("kgemm(Tensor(a!) out, Tensor x, Tensor w, int bm, int epi, float eps, Tensor? ss_in, "
         "Tensor(b!)? ss_out, Tensor(c!)? aout, Tensor? ln_out) -> ()");
-  m.def("dgemm_ok(int M, int N, int K, int splitk, int pf) -> bool");
   m.def("l2_prefetch(Tensor[] ts, Tensor(a!) sink) -> ()");
   m.def("car_create(int device, int rank, int world, int max_elems, int blocks=128) -> int");
   m.def("car_ipc_handles(int h) -> Tensor");
@@ -1389,7 +1361,6 @@ TORCH_LIBRARY(akap, m) {
 
 TORCH_LIBRARY_IMPL(akap, CompositeExplicitAutograd, m) {
   m.impl("gemm_splitk", &gemm_splitk);
-  m.impl("dgemm_ok", &dgemm_ok);
   m.impl("car_create", &car_create);
   m.impl("car_ipc_handles", &car_ipc_handles);
   m.impl("car_open", &car_open);

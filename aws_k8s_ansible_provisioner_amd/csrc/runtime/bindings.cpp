@@ -4,6 +4,7 @@
 #include <pybind11/stl.h>
 
 #include "block_manager.h"
+#include "host_contract.h"
 #include "scheduler.h"
 
 namespace py = pybind11;
@@ -57,6 +58,36 @@ static py::dict step_info(const StepInfo& i) {
   return d;
 }
 
+// csrc/kernels/host_contract.h as the submodule `contract`: the kernels' constants, support
+// predicates and workspace sizes, for Python that must work where the HIP library cannot load
+static void bind_contract(py::module_ m) {
+  using namespace akap;
+  m.attr("CTR_STRIDE") = kCtrStride;
+  m.attr("GEMM_CTR_INTS") = kCtrInts;
+  m.attr("GEMM_CTR_ERR") = kCtrErr;
+  m.attr("DECODE_MAX_PART") = kDecodeMaxPart;
+  m.attr("SAMPLE_MAX_CHUNKS") = kMaxChunks;
+  m.attr("SAMPLE_WS_PER_ROW") = sample_ws_floats(1);
+  m.attr("QGEMM_MAX_M") = QGEMM_MAX_M;
+  m.def("sample_ws_floats", &sample_ws_floats);
+  m.def("gemm_splitk_choice", &gemm_splitk_choice);
+  m.def("gdgemm_ws_floats", &gdgemm_ws_floats);
+  m.def("kgemm_supported", &kgemm_supported);
+  m.def("pgemm_supported", &pgemm_supported);
+  m.def("qgemm_supported", &qgemm_supported);
+  m.def("qgemm_geometry", [](int M, int N, int K) {
+    const QGemmGeom g = qgemm_geometry(M, N, K);
+    return py::make_tuple(g.bm, g.bn, g.grid);
+  });
+  m.def("moe_router_topk_supported", &moe_router_topk_supported);
+  // -> (supported, family 0 ring | 1 lds | 2 pgemm_sk, combines in launch, ws floats, ticket ints)
+  m.def("dgemm_contract", [](int M, int N, int K, int pro, int epi, int splitk, int pf, int bn,
+                             int ns, int bm, bool inlaunch, int cus) {
+    const DGemmContract c = dgemm_contract(M, N, K, pro, epi, splitk, pf, bn, ns, bm, inlaunch, cus);
+    return py::make_tuple(c.supported, c.family, c.inlaunch, c.ws_floats, c.ticket_ints);
+  });
+}
+
 #ifndef AKAP_RT_HASH
 #define AKAP_RT_HASH "unknown"
 #endif
@@ -65,6 +96,7 @@ PYBIND11_MODULE(_runtime, m) {
   m.doc() = "MI355X serving engine host runtime: paged KV block manager + batch scheduler";
   // digest of the runtime sources this module was compiled from (build_ext.runtime_tree_hash)
   m.def("build_hash", [] { return std::string(AKAP_RT_HASH); });
+  bind_contract(m.def_submodule("contract", "host-side contract of the gfx950 kernels"));
 
   py::class_<BlockManager>(m, "BlockManager")
       .def(py::init<int, int, bool>(), py::arg("num_blocks"), py::arg("block_size"),

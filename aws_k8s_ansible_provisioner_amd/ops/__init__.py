@@ -17,6 +17,7 @@ from typing import Optional
 
 import torch
 
+from .._runtime_loader import contract as _contract
 from . import reference as ref
 from .gemm_variant import Variant
 from .quant import Fp8Weight, linear_fp8, quantize_fp8  # noqa: F401
@@ -71,6 +72,18 @@ def native_provenance() -> dict:
 
 def native_available() -> bool:
     return load_native(False)
+
+
+# The kernels' host-side contract (csrc/kernels/host_contract.h) is read through _contract():
+# the CPU-built _runtime module, loaded on first use.  These module attributes are its constants.
+_CONTRACT_CONSTANTS = ("CTR_STRIDE", "GEMM_CTR_INTS", "GEMM_CTR_ERR", "DECODE_MAX_PART",
+                       "SAMPLE_MAX_CHUNKS", "SAMPLE_WS_PER_ROW")
+
+
+def __getattr__(name: str):
+    if name in _CONTRACT_CONSTANTS:
+        return getattr(_contract(), name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def _native(t: torch.Tensor) -> bool:
@@ -203,10 +216,6 @@ def check_qprep_positions(positions, seq_lens, q_start, table_rows: int) -> None
                              f"table's {table_rows} rows")
 
 
-# longest decode split-KV partition the kernel takes (csrc/kernels/kernels.h kDecodeMaxPart)
-DECODE_MAX_PART = 8192
-
-
 def paged_attention_decode(out, q, k_cache, v_cache, block_tables, seq_lens, gqa_group: int,
                            scale: float, workspace=None, num_parts: int = 1,
                            part_size: int = 512, q_start=None, v_tail=None, tail_slot=None):
@@ -276,16 +285,14 @@ PGEMM_MIN_M = int(os.environ.get("AKAP_PGEMM_MIN_M", "1024"))
 
 
 def pgemm_supported(M: int, N: int, K: int) -> bool:
-    """Mirror of pgemm_supported (csrc/kernels/pgemm.hip) and the 2 GiB operand limit of its
-    buffer-descriptor DMA (ops.cpp)."""
-    return (M > 0 and N > 0 and N % 256 == 0 and K >= 64 and K % 64 == 0
-            and M * K * 2 < 2 ** 31 and N * K * 2 < 2 ** 31)
+    """Whether pgemm takes a dense x [M, K] against an [N, K] weight."""
+    return _contract().pgemm_supported(M, N, K, K)
 
 
 def use_pgemm(x: torch.Tensor, N: int, silu: bool = False, grouped: bool = False) -> bool:
     """Route x [M, K] times an [N, K] weight (or a grouped [G, N, K] one) to pgemm?"""
     if not (x.is_cuda and x.dim() == 2 and x.stride(-1) == 1 and x.shape[0] >= PGEMM_MIN_M
-            and pgemm_supported(x.shape[0], N, x.shape[1])):
+            and _contract().pgemm_supported(x.shape[0], N, x.shape[1], x.stride(0))):
         return False
     if PREFILL_GEMM == "pgemm":
         return True
@@ -457,50 +464,38 @@ def dgemm(x: torch.Tensor, w: torch.Tensor, pro: int = PRO_PLAIN, splitk: int = 
     return out
 
 
+def _dgemm_contract(M: int, N: int, K: int, pro: int, epi: int, splitk: int, pf: int, bn: int,
+                    ns: int, bm: int, inlaunch: bool) -> tuple:
+    """dgemm_contract of host_contract.h, which torch.ops.akap.dgemm checks its tensors against:
+    (supported, family, K slices combined in the launch, fp32 workspace floats, ticket ints).
+    The last three follow from M, N and the variant alone."""
+    cus = device_cus() if bn == 256 else 0  # only the 256 x 256 body asks for the CU count
+    return _contract().dgemm_contract(M, N, K, pro, epi, splitk, pf, bn, ns, bm, bool(inlaunch),
+                                      cus)
+
+
 def _combines_in_launch(splitk: int, bn: int, inlaunch: bool, pro: int = PRO_PLAIN) -> bool:
-    """Whether a dgemm launch asked for inlaunch combines its K slices itself: every LDS-DMA
-    variant can; the register ring only with the plain prologue and 2 | 4 | 8 slices."""
-    return bool(inlaunch and splitk > 1 and (bn or (pro == PRO_PLAIN and splitk in (2, 4, 8))))
+    """Whether a dgemm launch asked for inlaunch combines its K slices itself."""
+    return _dgemm_contract(0, 0, 0, pro, EPI_STORE, splitk, 1, bn, 0, 64, inlaunch)[2]
 
 
 def dgemm_workspace(M: int, N: int, v: Variant, pro: int, device):
     """(fp32 split-K workspace, tile tickets or None) one torch.ops.akap.dgemm launch of
-    variant v needs -- the only place that sizes them (ops.cpp refuses an undersized one)."""
-    if v.splitk == 1:
-        return _empty_f32(device), None
-    inl = _combines_in_launch(v.splitk, v.bn, v.inlaunch, pro)
-    n = (gdgemm_ws_floats(M, N, v.splitk, v.bn or 64, v.bm if v.bn else 64) if (v.bn or inl) else
-         v.splitk * M * N + (v.splitk * M if pro == PRO_ADDNORM else 0))
-    ws = torch.empty(n, dtype=torch.float32, device=device)
-    # tickets: the probe-only 256 x 256 body always combines in the launch
-    return ws, gemm_counters(device) if (inl or v.probe_only) else None
+    variant v needs, as ops.cpp checks them."""
+    _, _, _, ws_floats, ticket_ints = _dgemm_contract(M, N, 0, pro, EPI_STORE, v.splitk, v.pf,
+                                                      v.bn, v.ns, v.bm, v.inlaunch)
+    ws = (torch.empty(ws_floats, dtype=torch.float32, device=device) if ws_floats else
+          _empty_f32(device))
+    return ws, gemm_counters(device) if ticket_ints else None
 
 
 def dgemm_supported(M: int, N: int, K: int, splitk: int, pf: int, epi: int = EPI_STORE,
                     bn: int = 0, inlaunch: bool = False, bm: int = 64) -> bool:
-    """Mirror of dgemm_supported / gdgemm_supported / dgemm_epi_supported (host-side)."""
-    if bn == 256:  # pgemm_sk: 256 x 256 tiles, any split, grid <= the CU count
-        if bm != 256 or N % 256 or K % 64 or not 1 <= splitk <= 32 or K // 64 < splitk:
-            return False
-        return -(-M // 256) * (N // 256) * splitk <= device_cus()
-    if splitk not in (1, 2, 4, 8, 16):
-        return False
-    if bm != 64 and not (bm == 128 and bn == 128) and not (bm == 256 and bn in (64, 128)):
-        return False
-    inl = _combines_in_launch(splitk, bn, inlaunch)
-    if inlaunch and splitk > 1 and not inl:
-        return False  # the register-ring combine has 2 | 4 | 8 slices
-    if epi == EPI_SILU and ((splitk != 1 and not inl) or N % 32):
-        return False
-    if epi == EPI_RESNORM and splitk > 1 and N % 256 and not inl:
-        return False
-    if bn:
-        if bn not in (64, 128) or M <= 0 or N % 4 or K % splitk:
-            return False
-        return (K // splitk) % 64 == 0
-    if M <= 0 or N <= 0 or K <= 0 or N % 4 or pf not in (1, 2, 4, 8) or K % splitk:
-        return False
-    return (K // splitk) % (64 * pf) == 0
+    """Whether torch.ops.akap.dgemm takes the launch (plain prologue), as a variant of its
+    own: a split-K variant asking for the in-launch combine must get it (the register ring
+    with 16 slices would run as its separate-reduce twin)."""
+    ok, _, inl, _, _ = _dgemm_contract(M, N, K, PRO_PLAIN, epi, splitk, pf, bn, 0, bm, inlaunch)
+    return ok and (inl or not inlaunch or splitk == 1)
 
 
 _CUS: dict = {}
@@ -521,21 +516,15 @@ def device_cus(device=None) -> int:
 
 
 def kgemm_supported(M: int, N: int, K: int, km: int, epi: int = EPI_STORE, pro: int = 0) -> bool:
-    """Mirror of kgemm_supported (csrc/kernels/kgemm.hip)."""
-    return (pro == PRO_PLAIN and km in (16, 32) and M > 0 and N % 32 == 0 and K >= 256
-            and K % 256 == 0 and epi in (EPI_STORE, EPI_RESNORM))
+    return pro == PRO_PLAIN and _contract().kgemm_supported(M, N, K, km, epi)
 
 
 def gdgemm_ws_floats(M: int, N: int, splitk: int, bn: int, bm: int = 64) -> int:
-    """fp32 workspace of a split-K LDS-DMA GEMM (tile-padded slabs; mirrors gdgemm.hip)."""
-    slabs = splitk * -(-M // bm) * -(-N // bn) * bm * bn
-    return max(slabs, splitk * M * N)
+    """fp32 workspace of a split-K LDS-DMA GEMM combined in the launch (tile-padded slabs)."""
+    return _contract().gdgemm_ws_floats(M, N, splitk, bn, bm)
 
 
 _COUNTERS: dict = {}
-CTR_STRIDE = 32  # ints per ticket counter: one 128-B L2 line each (csrc/kernels/common.h)
-GEMM_CTR_INTS = 1 << 18  # kCtrInts
-GEMM_CTR_ERR = GEMM_CTR_INTS - 1  # kCtrErr: an in-launch combine timed out
 
 
 def gemm_counters(device) -> torch.Tensor:
@@ -543,16 +532,17 @@ def gemm_counters(device) -> torch.Tensor:
     (launches on one stream are ordered; each tile's last arriver re-arms its counter)."""
     c = _COUNTERS.get(device)
     if c is None:
-        c = _COUNTERS[device] = torch.zeros(GEMM_CTR_INTS, dtype=torch.int32, device=device)
+        c = _COUNTERS[device] = torch.zeros(_contract().GEMM_CTR_INTS, dtype=torch.int32, device=device)
     return c
 
 
 def gemm_ctr_error(device, clear: bool = True) -> int:
     """The in-launch combines' timeout flag (probe-only bn = 256 variant); host sync."""
     c = gemm_counters(device)
-    v = int(c[GEMM_CTR_ERR].item())
+    err = _contract().GEMM_CTR_ERR
+    v = int(c[err].item())
     if clear and v:
-        c[GEMM_CTR_ERR].zero_()
+        c[err].zero_()
     return v
 
 
@@ -569,20 +559,11 @@ def _empty_f32(device) -> torch.Tensor:
 
 def gemm_splitk(M: int, N: int, K: int) -> int:
     """Split-K factor for the decode GEMM: enough 64x64 tiles x splits to cover 256 CUs,
-    each split keeping >= 256 of K (mirrors gemm_splitk_choice in gemm.hip)."""
-    tiles = ((M + 63) // 64) * ((N + 63) // 64)
-    s = 1
-    while tiles * s < 256 and K // (s * 2) >= 256:
-        s *= 2
-    return s
+    each split keeping >= 256 of K."""
+    return _contract().gemm_splitk_choice(M, N, K)
 
 
 # ----------------------------------------------------------------------------- sampling
-SAMPLE_MAX_CHUNKS = 64  # csrc/kernels/sampling.hip kMaxChunks
-# floats per row (sample_ws_floats): 64 chunk records of 8, a 16-word filter state,
-# 2 x kHistRow floats of filter-pass histograms (kHistRow = 64 x 512 float2), and the draw
-# rows' tile masses (64 chunks x kMaxTiles = 64)
-SAMPLE_WS_PER_ROW = SAMPLE_MAX_CHUNKS * 8 + 16 + 2 * SAMPLE_MAX_CHUNKS * 512 + SAMPLE_MAX_CHUNKS * 64
 _SAMPLE_WS: dict = {}
 _SAMPLE_OLD: list = []  # outgrown workspaces stay alive: captured hipGraphs address them
 
@@ -593,12 +574,13 @@ def _sample_ws(device, B: int):
     chunk re-arms its ticket in the kernel).  Grown, never
     shrunk: a decode hipGraph keeps the addresses it was captured with."""
     cur = _SAMPLE_WS.get(device)
-    if cur is None or cur[1].numel() < B * CTR_STRIDE:
+    c = _contract()
+    if cur is None or cur[1].numel() < B * c.CTR_STRIDE:
         if cur is not None:
             _SAMPLE_OLD.append(cur)
         n = max(B, 256)
-        cur = (torch.zeros(n * SAMPLE_WS_PER_ROW, dtype=torch.float32, device=device),
-               torch.zeros(n * CTR_STRIDE, dtype=torch.int32, device=device))
+        cur = (torch.zeros(c.sample_ws_floats(n), dtype=torch.float32, device=device),
+               torch.zeros(n * c.CTR_STRIDE, dtype=torch.int32, device=device))
         _SAMPLE_WS[device] = cur
     return cur
 
@@ -701,8 +683,8 @@ def moe_router_topk(h, router, top_k: int, renormalize: bool = True):
     """Router logits (bf16, as F.linear(h, router)) -> softmax -> top-k in one launch on the
     GPU for <= 16 experts (csrc/kernels/moe.hip); the two-step path otherwise."""
     T, E = h.shape[0], router.shape[0]
-    if (_native(h) and E <= 16 and T <= 2048 and h.shape[1] % 8 == 0 and h.stride(-1) == 1
-            and h.stride(0) % 8 == 0):  # prefill-sized T: hipBLASLt + top-k is cheaper
+    if (_native(h) and _contract().moe_router_topk_supported(E, h.shape[1]) and T <= 2048
+            and h.stride(-1) == 1 and h.stride(0) % 8 == 0):  # large T: hipBLASLt + top-k is cheaper
         w = torch.empty(T, top_k, dtype=torch.float32, device=h.device)
         ids = torch.empty(T, top_k, dtype=torch.int32, device=h.device)
         torch.ops.akap.moe_router_topk(h, router, w, ids, renormalize)

@@ -15,8 +15,15 @@ from typing import Optional
 
 import torch
 
+from .._runtime_loader import contract as _contract
+
 FP8_MAX = 448.0
-QGEMM_MAX_M = 256  # rows one qgemm launch covers (decode buckets); above: dequantize + bf16 GEMM
+
+
+def __getattr__(name: str):
+    if name == "QGEMM_MAX_M":  # rows one qgemm launch covers; above: dequantize + bf16 GEMM
+        return _contract().QGEMM_MAX_M
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 class Fp8Weight:
@@ -138,13 +145,15 @@ def dequant_fp8(w: Fp8Weight, out: Optional[torch.Tensor] = None) -> torch.Tenso
 
 
 def qgemm_supported(x: torch.Tensor, w: Fp8Weight, out: Optional[torch.Tensor] = None) -> bool:
-    """Mirror of qgemm_supported (csrc/kernels/qgemm.hip) and the alignment checks of ops.cpp."""
+    """Whether torch.ops.akap.qgemm takes the launch: the kernel's shape predicate and the
+    tensor properties ops.cpp checks (out=None: a fresh dense [M, N] output)."""
     N, K = w.shape
-    return (x.dim() == 2 and 0 < x.shape[0] <= QGEMM_MAX_M and x.dtype == torch.bfloat16
-            and x.stride(-1) == 1 and K >= 64 and K % 64 == 0 and N % 8 == 0
-            and x.stride(0) % 8 == 0 and x.data_ptr() % 16 == 0
+    return (x.dim() == 2 and x.dtype == torch.bfloat16 and x.stride(-1) == 1
+            and x.data_ptr() % 16 == 0
             and (out is None or (out.dim() == 2 and out.stride(-1) == 1
-                                 and out.stride(0) % 8 == 0 and out.data_ptr() % 16 == 0)))
+                                 and out.data_ptr() % 16 == 0))
+            and _contract().qgemm_supported(x.shape[0], N, K, x.stride(0),
+                                            N if out is None else out.stride(0)))
 
 
 def linear_fp8(x: torch.Tensor, w: Fp8Weight, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -29,7 +29,7 @@ import time
 import pytest
 import torch
 
-from aws_k8s_ansible_provisioner_amd import ops
+from aws_k8s_ansible_provisioner_amd import _runtime_loader, ops
 from aws_k8s_ansible_provisioner_amd.ops import reference as ref
 from aws_k8s_ansible_provisioner_amd.ops.gemm_variant import Variant
 
@@ -401,6 +401,43 @@ def test_exact_pgemm_sk(case):
     run_dcase(case, "pgemm_sk")
 
 
+# --------------------------------------------------- the launch contract the binding checks
+CONTRACT_VARIANTS = [Variant(2, 2), Variant(2, 2, inlaunch=True), Variant(2, 1, 64),
+                     Variant(2, 1, 128, inlaunch=True)]
+
+
+@pytest.mark.parametrize("v", CONTRACT_VARIANTS, ids=lambda v: f"s{v.splitk}{v.name}")
+def test_contract_sizes_are_what_the_binding_accepts(v):
+    """A workspace and tickets of exactly the sizes dgemm_contract (host_contract.h) gives are
+    accepted by torch.ops.akap.dgemm and the result is bit-exact; one float less, or one ticket
+    line less, is refused by the host check before anything is launched."""
+    M, N, K = 16, 256, 512
+    ok, _, inl, ws_floats, ticket_ints = ops._dgemm_contract(
+        M, N, K, ops.PRO_PLAIN, STORE, v.splitk, v.pf, v.bn, v.ns, v.bm, v.inlaunch)
+    assert ok and inl == v.inlaunch and ws_floats >= v.splitk * M * N
+    assert (ticket_ints > 0) == v.inlaunch
+    o, yi = oracle(M, N, K, vmax_for(K, N, STORE))
+    x, w = o.x.to(DEV), o.w.to(DEV)
+    out = torch.full((M, N), SENT, dtype=torch.bfloat16, device=DEV)
+
+    def launch(ws, tickets):
+        torch.ops.akap.dgemm(out, x, w, ws, ops.PRO_PLAIN, v.splitk, v.pf, None, None, None, EPS,
+                             STORE, None, None, None, None, v.bn, v.ns, tickets, v.bm)
+
+    ws = torch.empty(ws_floats, dtype=torch.float32, device=DEV)
+    tickets = torch.zeros(ticket_ints, dtype=torch.int32, device=DEV) if ticket_ints else None
+    with pytest.raises(RuntimeError, match="workspace"):
+        launch(ws[:-1], tickets)
+    if tickets is not None:
+        with pytest.raises(RuntimeError, match="counters"):
+            launch(ws, tickets[:-ops.CTR_STRIDE])
+    torch.cuda.synchronize()
+    assert bool((out == SENT).all()), "a refused launch wrote its output"
+    launch(ws, tickets)
+    assert_bits(out, ref.exact_gemm_expected(yi, o.unit, STORE).out, "y")
+    assert tickets is None or not bool(tickets.any()), "ticket left set"
+
+
 # ------------------------------------------------------------------------------- gemm.hip
 # (M, N, K, in-launch): split-K from ops.gemm_splitk
 GEMM_CASES = [(37, 1000, 2048, False), (37, 1000, 2048, True), (300, 1000, 64, False),
@@ -511,14 +548,8 @@ def test_exact_pgemm(case):
 
 # ------------------------------------------------------------------------------- qgemm.hip
 def qgemm_geometry(M, N):
-    """Mirror of qgemm_geometry (csrc/kernels/qgemm.hip): (bm, bn)."""
-    bm = 16 if M <= 16 else 32 if M <= 32 else 64
-    tiles_m = -(-M // bm)
-    if -(-N // 64) * tiles_m >= 256:
-        return bm, 64
-    if bm == 16 and -(-N // 32) <= 128:
-        return bm, 16
-    return bm, 32
+    """(bm, bn) of the tile launch_qgemm picks (qgemm_geometry of host_contract.h)."""
+    return _runtime_loader.contract().qgemm_geometry(M, N, 64)[:2]
 
 
 # one shape per geometry qgemm_geometry returns for M <= 256
