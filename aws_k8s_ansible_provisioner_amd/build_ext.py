@@ -62,7 +62,7 @@ def _digest(files: list[str], extra: str = "") -> str:
 def kernel_sources() -> list[str]:
     return sorted(glob.glob(os.path.join(CSRC, "kernels", "*.hip")) +
                   glob.glob(os.path.join(CSRC, "kernels", "*.h")) +
-                  [os.path.join(CSRC, "ops.cpp")])
+                  [os.path.join(CSRC, "ops.cpp"), os.path.join(CSRC, "op_args.h")])
 
 
 def runtime_sources() -> list[str]:
@@ -141,7 +141,8 @@ def build_kernels(force: bool = False, jobs: int = 8, log=None) -> str:
     cmd = [HIPCC, *common, "-D__HIP_PLATFORM_AMD__=1", "-DUSE_ROCM=1",
            "-DTORCH_EXTENSION_NAME=_C", *incs, "-I", "/opt/rocm/include", "-x", "c++", "-c",
            ops_src, "-o", ops_obj]
-    digest = _digest([ops_src] + headers, " ".join(cmd[:-3]) + f";torch={tv}")
+    digest = _digest([ops_src, os.path.join(CSRC, "op_args.h")] + headers,
+                     " ".join(cmd[:-3]) + f";torch={tv}")
     why = "forced" if force else _stale(ops_obj, digest)
     if why:
         log(f"compile ops.cpp ({why})")

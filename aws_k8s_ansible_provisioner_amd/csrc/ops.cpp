@@ -3,57 +3,97 @@
 // Every op launches on the caller's current HIP stream, allocates nothing and
 // never synchronises, so all of them are hipGraph-capturable (engine decode path).
 // PyTorch on ROCm names the GPU dispatch key "CUDA"; kernels are HIP/CDNA4 only.
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 #include <torch/library.h>
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
-#include <c10/core/DeviceGuard.h>
 
 #include "kernels/kernels.h"
+#include "op_args.h"
+
+// `data_ptr` appears in this file only in the functions below; every other pointer that
+// reaches a launch comes from an akap::OpArgs accessor (op_args.h).  tests/test_op_args.py
+// audits this list:
+//   h2d_stage        the source is pinned HOST memory, mapped with hipHostGetDevicePointer
+//   car_ipc_handles  fills a host byte blob with the two IPC handles
+//   car_open         reads the gathered host blob of IPC handles
+//   ipc_export       asks the runtime for the allocation around the address; fills a host blob
+//   ipc_open         reads a host blob (IPC handle + offset)
 
 namespace {
 
 using at::Tensor;
+using akap::OpArgs, akap::kAlign16, akap::kContig, akap::kLastContig;
 
 hipStream_t cur_stream() { return c10::hip::getCurrentHIPStream().stream(); }
 
-// KV caches are bf16, or uint8 holding OCP e4m3fn bytes (--kv-cache-dtype fp8)
-int kv_fp8_of(const Tensor& k_cache, const Tensor& v_cache) {
-  const bool f8 = k_cache.scalar_type() == at::kByte;
-  TORCH_CHECK(f8 || k_cache.scalar_type() == at::kBFloat16, "KV cache must be bf16 or uint8 (fp8)");
-  TORCH_CHECK(v_cache.scalar_type() == k_cache.scalar_type(), "K and V cache dtypes differ");
-  return f8 ? 1 : 0;
+// The accessor (and device guard) of op `op`, anchored on its tensor `t`, which must be on a GPU
+OpArgs on_gpu(const char* op, const Tensor& t, const char* name) {
+  TORCH_CHECK(t.defined() && t.is_cuda(), op, ": ", name, " must be a GPU tensor");
+  return OpArgs(op, t.device());
 }
 
-#define CHECK_GPU(x) TORCH_CHECK((x).is_cuda(), #x " must be a GPU tensor")
-#define CHECK_BF16(x) TORCH_CHECK((x).scalar_type() == at::kBFloat16, #x " must be bf16")
-#define CHECK_LAST_CONTIG(x) TORCH_CHECK((x).stride(-1) == 1, #x " must have unit last stride")
-#define CHECK_CONTIG(x) TORCH_CHECK((x).is_contiguous(), #x " must be contiguous")
-
 void rmsnorm(Tensor out, Tensor x, Tensor w, double eps) {
-  CHECK_GPU(x); CHECK_BF16(x); CHECK_BF16(w); CHECK_BF16(out);
-  CHECK_LAST_CONTIG(x); CHECK_LAST_CONTIG(out);
+  const OpArgs a = on_gpu("rmsnorm", x, "x");
   const int d = x.size(-1);
-  TORCH_CHECK(d % 8 == 0, "hidden size must be a multiple of 8");
+  TORCH_CHECK(d % 8 == 0, "rmsnorm: hidden size must be a multiple of 8");
   const int rows = x.numel() / d;
-  const c10::DeviceGuard g(x.device());
-  akap::launch_rmsnorm(out.data_ptr(), x.data_ptr(), w.data_ptr(), rows, d,
+  akap::launch_rmsnorm(a.bf16(out, "out", (int64_t)rows * d, kLastContig),
+                       a.bf16(x, "x", 0, kLastContig), a.bf16(w, "w", d), rows, d,
                        x.dim() > 1 ? x.stride(-2) : d, out.dim() > 1 ? out.stride(-2) : d,
                        (float)eps, cur_stream());
 }
 
 void fused_add_rmsnorm(Tensor out, Tensor residual, Tensor x, Tensor w, double eps) {
-  CHECK_GPU(x); CHECK_BF16(x); CHECK_BF16(residual); CHECK_BF16(w); CHECK_BF16(out);
-  CHECK_CONTIG(residual); CHECK_LAST_CONTIG(x); CHECK_LAST_CONTIG(out);
+  const OpArgs a = on_gpu("fused_add_rmsnorm", x, "x");
   const int d = x.size(-1);
-  TORCH_CHECK(d % 8 == 0, "hidden size must be a multiple of 8");
+  TORCH_CHECK(d % 8 == 0, "fused_add_rmsnorm: hidden size must be a multiple of 8");
   const int rows = x.numel() / d;
-  const c10::DeviceGuard g(x.device());
-  akap::launch_fused_add_rmsnorm(out.data_ptr(), residual.data_ptr(), x.data_ptr(), w.data_ptr(),
-                                 rows, d, x.dim() > 1 ? x.stride(-2) : d,
+  akap::launch_fused_add_rmsnorm(a.bf16(out, "out", (int64_t)rows * d, kLastContig),
+                                 a.bf16(residual, "residual", (int64_t)rows * d),
+                                 a.bf16(x, "x", 0, kLastContig), a.bf16(w, "w", d), rows, d,
+                                 x.dim() > 1 ? x.stride(-2) : d,
                                  out.dim() > 1 ? out.stride(-2) : d, (float)eps, cur_stream());
+}
+
+// The paged KV cache of one layer: K [NB, Hkv, BS, 128] and V [NB, Hkv, BS/8, 128, 8] (8-token
+// groups), both contiguous and both bf16, or both uint8 holding OCP e4m3fn bytes
+// (--kv-cache-dtype fp8); BS a multiple of 32 (K cache chunk layout).
+struct KVCache { int fp8, Hkv, BS; void *k, *v; };
+KVCache kv_cache_of(const OpArgs& a, const Tensor& k_cache, const Tensor& v_cache) {
+  KVCache c{};
+  c.k = a.ptr(k_cache, "k_cache", {at::kBFloat16, at::kByte});
+  c.v = a.ptr(v_cache, "v_cache", {k_cache.scalar_type()});
+  TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(3) == 128, a.op(),
+              ": k_cache must be [NB,Hkv,BS,128] (head_dim 128)");
+  c.fp8 = k_cache.scalar_type() == at::kByte;
+  c.Hkv = k_cache.size(1);
+  c.BS = k_cache.size(2);
+  TORCH_CHECK(c.BS % 32 == 0, a.op(),
+              ": k_cache block size must be a multiple of 32 (K cache chunk layout)");
+  TORCH_CHECK(v_cache.dim() == 5 && v_cache.size(0) == k_cache.size(0) &&
+                  v_cache.size(1) == c.Hkv && v_cache.size(2) * 8 == c.BS &&
+                  v_cache.size(3) == 128 && v_cache.size(4) == 8,
+              a.op(), ": v_cache must be [NB,Hkv,BS/8,128,8] beside k_cache [NB,Hkv,BS,128]");
+  return c;
+}
+
+// The V tail: v_tail contiguous bf16 [slots, Hkv, 8, 128] (a bf16 cache only) with tail_slot,
+// int32 with at least `rows` entries; both null when v_tail is absent
+struct VTail { void* v_tail; const int* tail_slot; };
+VTail v_tail_of(const OpArgs& a, const KVCache& kv, const std::optional<Tensor>& v_tail,
+                const std::optional<Tensor>& tail_slot, int rows) {
+  if (!v_tail) return {nullptr, nullptr};
+  TORCH_CHECK(!kv.fp8, a.op(), ": v_tail needs a bf16 KV cache");
+  TORCH_CHECK(tail_slot.has_value(), a.op(), ": tail_slot must come with v_tail");
+  VTail t{a.bf16(*v_tail, "v_tail"), a.ptr<int>(*tail_slot, "tail_slot", rows)};
+  TORCH_CHECK(v_tail->dim() == 4 && v_tail->size(1) == kv.Hkv && v_tail->size(2) == 8 &&
+                  v_tail->size(3) == 128,
+              a.op(), ": v_tail must be contiguous bf16 [slots, Hkv, 8, 128]");
+  return t;
 }
 
 void qk_norm_rope_cache(Tensor qkv, Tensor q_out, Tensor k_cache, Tensor v_cache,
@@ -62,130 +102,145 @@ void qk_norm_rope_cache(Tensor qkv, Tensor q_out, Tensor k_cache, Tensor v_cache
                         int64_t Hkv, double eps, bool apply_rope, bool decode,
                         std::optional<Tensor> v_tail, std::optional<Tensor> tail_slot,
                         int64_t num_decode, int64_t q_rows) {
-  CHECK_GPU(qkv); CHECK_BF16(qkv); CHECK_LAST_CONTIG(qkv); CHECK_CONTIG(q_out);
-  TORCH_CHECK(q_rows >= -1 && q_rows <= qkv.size(0), "q_rows out of range");
-  CHECK_CONTIG(k_cache); CHECK_CONTIG(v_cache);
-  TORCH_CHECK(positions.scalar_type() == at::kLong && slots.scalar_type() == at::kLong,
-              "positions/slots must be int64");
-  TORCH_CHECK(cos_sin.scalar_type() == at::kFloat, "cos_sin cache must be fp32");
+  const OpArgs a = on_gpu("qk_norm_rope_cache", qkv, "qkv");
+  const KVCache kv = kv_cache_of(a, k_cache, v_cache);
+  TORCH_CHECK(qkv.dim() == 2 && Hq >= 0 && Hkv == kv.Hkv, a.op(),
+              ": qkv must be 2-D and Hkv the cache's");
   const int T = qkv.size(0);
-  const int D = k_cache.size(3);
-  const int BS = k_cache.size(2);
-  TORCH_CHECK(D == 128, "head_dim must be 128");
-  TORCH_CHECK(BS % 32 == 0, "block size must be a multiple of 32 (K cache chunk layout)");
-  TORCH_CHECK(v_cache.dim() == 5 && v_cache.size(2) * 8 == BS && v_cache.size(3) == D &&
-                  v_cache.size(4) == 8,
-              "v_cache must be [NB,Hkv,BS/8,D,8]");
-  TORCH_CHECK(qkv.size(1) >= (Hq + 2 * Hkv) * D, "qkv too narrow");
-  TORCH_CHECK(positions.numel() >= T && slots.numel() >= T, "positions/slots too short");
-  if (v_tail) {
-    TORCH_CHECK(!decode, "the V tail is written by the span (prefill / mixed) role only");
-    TORCH_CHECK(!kv_fp8_of(k_cache, v_cache), "the V tail needs a bf16 KV cache");
-    TORCH_CHECK(tail_slot && tail_slot->scalar_type() == at::kInt && tail_slot->numel() >= T,
-                "tail_slot: int32, one entry per token");
-    TORCH_CHECK(v_tail->scalar_type() == at::kBFloat16 && v_tail->dim() == 4 &&
-                    v_tail->size(1) == Hkv && v_tail->size(2) == 8 && v_tail->size(3) == D &&
-                    v_tail->is_contiguous(),
-                "v_tail must be contiguous bf16 [slots, Hkv, 8, 128]");
-    TORCH_CHECK(num_decode >= 0 && num_decode <= T, "num_decode out of range");
-  }
-  const c10::DeviceGuard g(qkv.device());
+  TORCH_CHECK(q_rows >= -1 && q_rows <= T, a.op(), ": q_rows out of range");
+  TORCH_CHECK(qkv.size(1) >= (Hq + 2 * Hkv) * 128, a.op(), ": qkv too narrow");
+  TORCH_CHECK(!v_tail || !decode, a.op(),
+              ": v_tail is written by the span (prefill / mixed) role only");
+  TORCH_CHECK(!v_tail || (num_decode >= 0 && num_decode <= T), a.op(),
+              ": num_decode out of range");
+  const VTail vt = v_tail_of(a, kv, v_tail, tail_slot, T);
   akap::launch_qk_norm_rope_cache(
-      qkv.data_ptr(), qkv.stride(0), q_out.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-      positions.data_ptr<int64_t>(), slots.data_ptr<int64_t>(), cos_sin.data_ptr<float>(),
-      q_w ? q_w->data_ptr() : nullptr, k_w ? k_w->data_ptr() : nullptr, T, Hq, Hkv, D, BS,
-      (float)eps, apply_rope ? 1 : 0, cur_stream(), kv_fp8_of(k_cache, v_cache), decode ? 1 : 0,
-      v_tail ? v_tail->data_ptr() : nullptr, v_tail ? tail_slot->data_ptr<int>() : nullptr,
-      (int)num_decode, (int)q_rows);
+      a.bf16(qkv, "qkv", 0, kLastContig), qkv.stride(0),
+      a.bf16(q_out, "q_out", (q_rows < 0 ? T : q_rows) * Hq * 128), kv.k, kv.v,
+      a.ptr<int64_t>(positions, "positions", T), a.ptr<int64_t>(slots, "slots", T),
+      a.ptr<float>(cos_sin, "cos_sin", apply_rope ? 128 : 0), a.bf16(q_w, "q_w", 128),
+      a.bf16(k_w, "k_w", 128), T, Hq, Hkv, 128, kv.BS, (float)eps, apply_rope ? 1 : 0,
+      cur_stream(), kv.fp8, decode ? 1 : 0, vt.v_tail, vt.tail_slot, (int)num_decode,
+      (int)q_rows);
 }
 
 void reshape_and_cache(Tensor k, Tensor v, Tensor k_cache, Tensor v_cache, Tensor slots) {
-  CHECK_GPU(k); CHECK_CONTIG(k); CHECK_CONTIG(v); CHECK_BF16(k); CHECK_BF16(v);
-  const int T = k.size(0), Hkv = k.size(1), D = k.size(2);
-  const int BS = k_cache.size(2);
-  TORCH_CHECK(D == 128, "head_dim must be 128");
-  TORCH_CHECK(BS % 32 == 0, "block size must be a multiple of 32 (K cache chunk layout)");
-  const c10::DeviceGuard g(k.device());
-  akap::launch_reshape_and_cache(k.data_ptr(), v.data_ptr(), k_cache.data_ptr(),
-                                 v_cache.data_ptr(), slots.data_ptr<int64_t>(), T, Hkv, D, BS,
-                                 cur_stream(), kv_fp8_of(k_cache, v_cache));
+  const OpArgs a = on_gpu("reshape_and_cache", k, "k");
+  const KVCache kv = kv_cache_of(a, k_cache, v_cache);
+  TORCH_CHECK(k.dim() == 3 && k.size(1) == kv.Hkv && k.size(2) == 128, a.op(),
+              ": k must be [T, Hkv, 128] with the cache's Hkv");
+  const int T = k.size(0);
+  akap::launch_reshape_and_cache(a.bf16(k, "k"), a.bf16(v, "v", k.numel()), kv.k, kv.v,
+                                 a.ptr<int64_t>(slots, "slots", T), T, kv.Hkv, 128, kv.BS,
+                                 cur_stream(), kv.fp8);
 }
 
 void silu_and_mul(Tensor out, Tensor x) {
-  CHECK_GPU(x); CHECK_BF16(x); CHECK_LAST_CONTIG(x); CHECK_CONTIG(out);
+  const OpArgs a = on_gpu("silu_and_mul", x, "x");
   const int F = x.size(-1) / 2;
-  TORCH_CHECK(F % 8 == 0, "ffn size must be a multiple of 8");
+  TORCH_CHECK(F % 8 == 0, "silu_and_mul: ffn size must be a multiple of 8");
   const long T = x.numel() / x.size(-1);
-  const c10::DeviceGuard g(x.device());
-  akap::launch_silu_and_mul(out.data_ptr(), x.data_ptr(), T, F,
+  akap::launch_silu_and_mul(a.bf16(out, "out", T * F), a.bf16(x, "x", 0, kLastContig), T, F,
                             x.dim() > 1 ? x.stride(-2) : 2 * F, cur_stream());
 }
 
-// V tail arguments: v_tail [slots, Hkv, 8, D] bf16 (a bf16 cache only), tail_slot int32 with
-// at least `rows` entries
-static void set_v_tail(akap::AttnParams& p, const std::optional<Tensor>& v_tail,
-                       const std::optional<Tensor>& tail_slot, int rows) {
-  p.v_tail = nullptr;
-  p.tail_slot = nullptr;
-  if (!v_tail) return;
-  TORCH_CHECK(tail_slot && tail_slot->scalar_type() == at::kInt && tail_slot->numel() >= rows,
-              "tail_slot: int32 with one entry per row");
-  TORCH_CHECK(v_tail->scalar_type() == at::kBFloat16 && v_tail->dim() == 4 &&
-                  v_tail->size(1) == p.Hkv && v_tail->size(2) == 8 && v_tail->size(3) == 128 &&
-                  v_tail->is_contiguous(),
-              "v_tail must be contiguous bf16 [slots, Hkv, 8, 128]");
-  TORCH_CHECK(!p.kv_fp8, "the V tail needs a bf16 KV cache");
-  p.v_tail = (__bf16*)v_tail->data_ptr();
-  p.tail_slot = tail_slot->data_ptr<int>();
-}
-
-akap::AttnParams attn_params(Tensor& out, Tensor& q, Tensor& k_cache, Tensor& v_cache,
-                             Tensor& block_tables, Tensor& seq_lens, int64_t G, double scale) {
-  CHECK_GPU(q); CHECK_BF16(q); CHECK_CONTIG(q); CHECK_CONTIG(out); CHECK_CONTIG(k_cache);
-  CHECK_CONTIG(v_cache);
-  TORCH_CHECK(block_tables.scalar_type() == at::kInt && seq_lens.scalar_type() == at::kInt,
-              "block_tables / seq_lens must be int32");
-  TORCH_CHECK(block_tables.stride(1) == 1, "block_tables rows must be contiguous");
+// What the four attention ops share: `q` is the q-shaped tensor [T, Hq, 128] (the ops that
+// read raw QKV rows pass `out`, same shape, and clear p.q), `rows` the q / out rows the launch
+// certainly touches (0: known to the device only), B the number of sequences.
+akap::AttnParams attn_params(const OpArgs& a, const KVCache& kv, Tensor& out, Tensor& q,
+                             Tensor& block_tables, Tensor& seq_lens, int64_t rows, int64_t G,
+                             double scale) {
+  TORCH_CHECK(q.dim() == 3 && q.size(2) == 128, a.op(), ": q / out must be [T, Hq, 128]");
+  const int B = seq_lens.numel();
   akap::AttnParams p{};
-  p.q = (const __bf16*)q.data_ptr();
-  p.kv_fp8 = kv_fp8_of(k_cache, v_cache);
-  p.k_cache = k_cache.data_ptr();
-  p.v_cache = v_cache.data_ptr();
-  p.out = (__bf16*)out.data_ptr();
-  p.block_tables = block_tables.data_ptr<int>();
-  p.bt_stride = block_tables.stride(0);
-  p.seq_lens = seq_lens.data_ptr<int>();
   p.Hq = q.size(1);
-  p.Hkv = k_cache.size(1);
+  p.Hkv = kv.Hkv;
   p.G = G;
-  p.BS = k_cache.size(2);
-  TORCH_CHECK(q.size(2) == 128 && k_cache.size(3) == 128, "attention kernels need head_dim 128");
-  TORCH_CHECK(v_cache.dim() == 5 && v_cache.size(4) == 8, "v_cache must be [NB,Hkv,BS/8,D,8]");
-  TORCH_CHECK(p.Hq == p.Hkv * G, "Hq must equal Hkv * G");
-  TORCH_CHECK(p.BS % 32 == 0, "block size must be a multiple of 32 (K cache chunk layout)");
+  p.BS = kv.BS;
+  TORCH_CHECK(p.Hq == p.Hkv * G, a.op(), ": Hq must equal Hkv * G");
+  p.q = (const __bf16*)a.bf16(q, "q", rows * p.Hq * 128);
+  p.out = (__bf16*)a.bf16(out, "out", q.numel());
+  p.kv_fp8 = kv.fp8;
+  p.k_cache = kv.k;
+  p.v_cache = kv.v;
+  TORCH_CHECK(block_tables.dim() == 2 && block_tables.size(0) >= B, a.op(),
+              ": block_tables must be [B, max_blocks], one row per sequence");
+  p.block_tables = a.ptr<int>(block_tables, "block_tables", 0, kLastContig);
+  p.bt_stride = block_tables.stride(0);
+  p.seq_lens = a.ptr<int>(seq_lens, "seq_lens");
   p.scale_log2 = (float)(scale * 1.4426950408889634);
   return p;
+}
+
+// The prefill tile map: q_start [B+1] and the per-tile sequence / first-row maps, int32;
+// tile_rows 128 | 256 (256: bf16 cache).  Returns the number of tiles.
+int set_prefill_tiles(const OpArgs& a, akap::AttnParams& p, const Tensor& block_tables,
+                      const Tensor& seq_lens, const Tensor& q_start, const Tensor& tile_seq,
+                      const Tensor& tile_row, int64_t tile_rows) {
+  TORCH_CHECK(tile_rows == 128 || tile_rows == 256, a.op(), ": tile_rows must be 128 or 256");
+  TORCH_CHECK(tile_rows != 256 || !p.kv_fp8, a.op(), ": tile_rows=256 needs a bf16 KV cache");
+  // the flash-style kernel caches a sequence's block ids in LDS: <= 32768 keys
+  TORCH_CHECK(block_tables.size(1) * p.BS <= 32768, a.op(),
+              ": prefill attention supports contexts up to 32768 tokens");
+  const int num_tiles = tile_seq.numel();
+  p.q_start = a.ptr<int>(q_start, "q_start", seq_lens.numel() + 1);
+  p.tile_seq = a.ptr<int>(tile_seq, "tile_seq");
+  p.tile_row = a.ptr<int>(tile_row, "tile_row", num_tiles);
+  return num_tiles;
+}
+
+// The raw-QKV source of the ops whose kernel applies the per-head RMSNorm + RoPE itself: qkv
+// bf16 [>= rows, >= (Hq + 2 Hkv) * 128] in 16-byte aligned rows (the kernels load 16-byte
+// vectors from them), positions int64, cos_sin contiguous fp32 [P, 128], q_w / k_w contiguous
+// bf16 [128] or absent.
+void set_raw_qkv(const OpArgs& a, akap::AttnParams& p, const Tensor& qkv, int64_t rows,
+                 const Tensor& positions, const Tensor& cos_sin,
+                 const std::optional<Tensor>& q_w, const std::optional<Tensor>& k_w,
+                 double eps) {
+  TORCH_CHECK(qkv.dim() == 2 && qkv.size(0) >= rows &&
+                  qkv.size(1) >= (p.Hq + 2 * p.Hkv) * 128,
+              a.op(), ": qkv must be [rows, >= (Hq + 2 Hkv) * 128]");
+  TORCH_CHECK(qkv.stride(0) % 8 == 0, a.op(), ": qkv rows must be 16-byte aligned");
+  TORCH_CHECK(cos_sin.dim() == 2 && cos_sin.size(1) == 128, a.op(),
+              ": cos_sin must be contiguous fp32 [max_pos, 128]");
+  TORCH_CHECK((!q_w || q_w->numel() == 128) && (!k_w || k_w->numel() == 128), a.op(),
+              ": q_w / k_w must be contiguous bf16 [128]");
+  p.q = nullptr;
+  p.qkv = (const __bf16*)a.bf16(qkv, "qkv", 0, kLastContig | kAlign16);
+  p.qkv_stride = qkv.stride(0);
+  p.positions = a.ptr<int64_t>(positions, "positions", rows);
+  p.cos_sin = a.ptr<float>(cos_sin, "cos_sin");
+  p.q_w = (const __bf16*)a.bf16(q_w, "q_w");
+  p.k_w = (const __bf16*)a.bf16(k_w, "k_w");
+  p.eps = (float)eps;
+}
+
+// The decode ops' split-KV fields: part_size, and with more than one part the fp32 partial
+// max / sum / output workspaces
+void set_split_kv(const OpArgs& a, akap::AttnParams& p, const Tensor& part_m,
+                  const Tensor& part_l, const Tensor& part_o, int64_t num_parts,
+                  int64_t part_size, int B) {
+  TORCH_CHECK(part_size % 128 == 0 && part_size > 0 && part_size <= akap::kDecodeMaxPart,
+              a.op(), ": part_size must be a multiple of 128, at most ", akap::kDecodeMaxPart);
+  p.num_parts = num_parts;
+  p.part_size = part_size;
+  if (num_parts <= 1) return;
+  const int64_t n = (int64_t)B * p.Hkv * num_parts * p.G;
+  p.part_m = a.ptr<float>(part_m, "part_m", n);
+  p.part_l = a.ptr<float>(part_l, "part_l", n);
+  p.part_o = a.ptr<float>(part_o, "part_o", n * 128);
 }
 
 void paged_attention_prefill(Tensor out, Tensor q, Tensor k_cache, Tensor v_cache,
                              Tensor block_tables, Tensor seq_lens, Tensor q_start,
                              Tensor tile_seq, Tensor tile_row, int64_t G, double scale,
                              int64_t tile_rows) {
-  auto p = attn_params(out, q, k_cache, v_cache, block_tables, seq_lens, G, scale);
-  TORCH_CHECK(tile_rows == 128 || tile_rows == 256, "tile_rows must be 128 or 256");
-  TORCH_CHECK(tile_rows != 256 || k_cache.scalar_type() == at::kBFloat16,
-              "tile_rows=256 needs a bf16 KV cache");
-  // the flash-style kernel caches a sequence's block ids in LDS: <= 32768 keys
-  TORCH_CHECK(block_tables.size(1) * k_cache.size(2) <= 32768,
-              "prefill attention supports contexts up to 32768 tokens");
-  TORCH_CHECK(q_start.scalar_type() == at::kInt && tile_seq.scalar_type() == at::kInt &&
-                  tile_row.scalar_type() == at::kInt,
-              "q_start/tile maps must be int32");
-  p.q_start = q_start.data_ptr<int>();
-  p.tile_seq = tile_seq.data_ptr<int>();
-  p.tile_row = tile_row.data_ptr<int>();
-  const c10::DeviceGuard g(q.device());
-  akap::launch_paged_attn_prefill(p, tile_seq.numel(), (int)tile_rows, cur_stream());
+  const OpArgs a = on_gpu("paged_attention_prefill", q, "q");
+  const KVCache kv = kv_cache_of(a, k_cache, v_cache);
+  auto p = attn_params(a, kv, out, q, block_tables, seq_lens, 0, G, scale);
+  const int num_tiles =
+      set_prefill_tiles(a, p, block_tables, seq_lens, q_start, tile_seq, tile_row, tile_rows);
+  akap::launch_paged_attn_prefill(p, num_tiles, (int)tile_rows, cur_stream());
 }
 
 // Prefill attention that reads its q rows raw from the QKV projection and applies the per-head
@@ -200,42 +255,16 @@ void paged_attention_prefill_qprep(Tensor out, Tensor qkv, Tensor k_cache, Tenso
                                    Tensor tile_seq, Tensor tile_row, Tensor positions,
                                    Tensor cos_sin, std::optional<Tensor> q_w, int64_t G,
                                    double scale, double eps, int64_t tile_rows) {
-  CHECK_GPU(qkv); CHECK_BF16(qkv); CHECK_LAST_CONTIG(qkv);
-  TORCH_CHECK(positions.scalar_type() == at::kLong && positions.numel() >= qkv.size(0),
-              "positions: int64, one per token");
-  TORCH_CHECK(cos_sin.scalar_type() == at::kFloat && cos_sin.is_contiguous() &&
-                  cos_sin.size(-1) == 128,
-              "cos_sin: contiguous fp32 [max_pos, 128]");
-  TORCH_CHECK(qkv.size(0) == out.size(0), "qkv / out token counts differ");
-  TORCH_CHECK(qkv.size(1) >= (out.size(1) + 2 * k_cache.size(1)) * 128, "qkv too narrow");
-  TORCH_CHECK(qkv.stride(0) % 8 == 0 && (uintptr_t)qkv.data_ptr() % 16 == 0,
-              "qkv rows must be 16-byte aligned");
-  if (q_w) {
-    CHECK_BF16(*q_w);
-    TORCH_CHECK(q_w->is_contiguous() && q_w->numel() == 128, "q_w: contiguous bf16 [128]");
-  }
+  const OpArgs a = on_gpu("paged_attention_prefill_qprep", qkv, "qkv");
+  const KVCache kv = kv_cache_of(a, k_cache, v_cache);
   // `out` doubles as the q-shaped tensor for the shared parameter checks (same [T, Hq, D])
-  auto p = attn_params(out, out, k_cache, v_cache, block_tables, seq_lens, G, scale);
-  TORCH_CHECK(tile_rows == 128 || tile_rows == 256, "tile_rows must be 128 or 256");
-  TORCH_CHECK(tile_rows != 256 || k_cache.scalar_type() == at::kBFloat16,
-              "tile_rows=256 needs a bf16 KV cache");
-  TORCH_CHECK(block_tables.size(1) * k_cache.size(2) <= 32768,
-              "prefill attention supports contexts up to 32768 tokens");
-  TORCH_CHECK(q_start.scalar_type() == at::kInt && tile_seq.scalar_type() == at::kInt &&
-                  tile_row.scalar_type() == at::kInt,
-              "q_start/tile maps must be int32");
-  p.q = nullptr;
-  p.qkv = (const __bf16*)qkv.data_ptr();
-  p.qkv_stride = qkv.stride(0);
-  p.positions = positions.data_ptr<int64_t>();
-  p.cos_sin = cos_sin.data_ptr<float>();
-  p.q_w = q_w ? (const __bf16*)q_w->data_ptr() : nullptr;
-  p.eps = (float)eps;
-  p.q_start = q_start.data_ptr<int>();
-  p.tile_seq = tile_seq.data_ptr<int>();
-  p.tile_row = tile_row.data_ptr<int>();
-  const c10::DeviceGuard g(qkv.device());
-  akap::launch_paged_attn_prefill(p, tile_seq.numel(), (int)tile_rows, cur_stream());
+  auto p = attn_params(a, kv, out, out, block_tables, seq_lens, 0, G, scale);
+  TORCH_CHECK(qkv.dim() == 2 && qkv.size(0) == out.size(0), a.op(),
+              ": qkv / out token counts differ");
+  set_raw_qkv(a, p, qkv, out.size(0), positions, cos_sin, q_w, std::nullopt, eps);
+  const int num_tiles =
+      set_prefill_tiles(a, p, block_tables, seq_lens, q_start, tile_seq, tile_row, tile_rows);
+  akap::launch_paged_attn_prefill(p, num_tiles, (int)tile_rows, cur_stream());
 }
 
 void paged_attention_decode(Tensor out, Tensor q, Tensor k_cache, Tensor v_cache,
@@ -243,24 +272,17 @@ void paged_attention_decode(Tensor out, Tensor q, Tensor k_cache, Tensor v_cache
                             Tensor part_m, Tensor part_l, Tensor part_o, int64_t num_parts,
                             int64_t part_size, int64_t G, double scale,
                             std::optional<Tensor> v_tail, std::optional<Tensor> tail_slot) {
-  auto p = attn_params(out, q, k_cache, v_cache, block_tables, seq_lens, G, scale);
-  TORCH_CHECK(G <= 16, "decode kernel supports up to 16 q heads per kv head");
-  set_v_tail(p, v_tail, tail_slot, seq_lens.numel());
-  TORCH_CHECK(part_size % 128 == 0 && part_size > 0 && part_size <= akap::kDecodeMaxPart,
-              "part_size must be a multiple of 128, at most ", akap::kDecodeMaxPart);
+  const OpArgs a = on_gpu("paged_attention_decode", q, "q");
+  const KVCache kv = kv_cache_of(a, k_cache, v_cache);
   const int B = seq_lens.numel();
-  p.q_start = q_start ? q_start->data_ptr<int>() : nullptr;
-  p.num_parts = num_parts;
-  p.part_size = part_size;
-  if (num_parts > 1) {
-    TORCH_CHECK(part_o.numel() >= (int64_t)B * p.Hkv * num_parts * G * 128,
-                "part_o workspace too small");
-    TORCH_CHECK(part_m.numel() >= (int64_t)B * p.Hkv * num_parts * G, "part_m too small");
-    p.part_m = part_m.data_ptr<float>();
-    p.part_l = part_l.data_ptr<float>();
-    p.part_o = part_o.data_ptr<float>();
-  }
-  const c10::DeviceGuard g(q.device());
+  // one q row per sequence unless q_start maps several to it
+  auto p = attn_params(a, kv, out, q, block_tables, seq_lens, q_start ? 0 : B, G, scale);
+  TORCH_CHECK(G <= 16, a.op(), ": the decode kernel supports up to 16 q heads per kv head");
+  const VTail vt = v_tail_of(a, kv, v_tail, tail_slot, B);
+  p.v_tail = (__bf16*)vt.v_tail;
+  p.tail_slot = vt.tail_slot;
+  p.q_start = a.ptr<int>(q_start, "q_start", B + 1);
+  set_split_kv(a, p, part_m, part_l, part_o, num_parts, part_size, B);
   akap::launch_paged_attn_decode(p, B, cur_stream());
 }
 
@@ -274,53 +296,34 @@ void paged_attention_decode_fused(Tensor out, Tensor qkv, Tensor k_cache, Tensor
                                   Tensor part_o, int64_t num_parts, int64_t part_size, int64_t G,
                                   double scale, double eps, std::optional<Tensor> v_tail,
                                   std::optional<Tensor> tail_slot) {
-  auto p = attn_params(out, out, k_cache, v_cache, block_tables, seq_lens, G, scale);
-  set_v_tail(p, v_tail, tail_slot, seq_lens.numel());
-  CHECK_GPU(qkv); CHECK_BF16(qkv); CHECK_LAST_CONTIG(qkv);
-  TORCH_CHECK(G + 2 <= 16, "fused decode supports up to 14 q heads per kv head");
-  TORCH_CHECK(part_size % 128 == 0 && part_size > 0 && part_size <= akap::kDecodeMaxPart,
-              "part_size must be a multiple of 128, at most ", akap::kDecodeMaxPart);
+  const OpArgs a = on_gpu("paged_attention_decode_fused", qkv, "qkv");
+  const KVCache kv = kv_cache_of(a, k_cache, v_cache);
   const int B = seq_lens.numel();
-  TORCH_CHECK(qkv.size(0) >= B && qkv.size(1) >= (p.Hq + 2 * p.Hkv) * 128, "qkv shape");
-  TORCH_CHECK(positions.scalar_type() == at::kLong && slots.scalar_type() == at::kLong,
-              "positions / slots must be int64");
-  TORCH_CHECK(positions.numel() >= B && slots.numel() >= B, "positions / slots too short");
-  TORCH_CHECK(cos_sin.scalar_type() == at::kFloat && cos_sin.size(1) == 128, "cos_sin [P, 128]");
-  p.q = nullptr;
-  p.qkv = (const __bf16*)qkv.data_ptr();
-  p.qkv_stride = qkv.stride(0);
-  p.positions = positions.data_ptr<int64_t>();
-  p.slots = slots.data_ptr<int64_t>();
-  p.cos_sin = cos_sin.data_ptr<float>();
-  p.q_w = q_w ? (const __bf16*)q_w->data_ptr() : nullptr;
-  p.k_w = k_w ? (const __bf16*)k_w->data_ptr() : nullptr;
-  p.eps = (float)eps;
+  // `out` doubles as the q-shaped tensor, as in the q-prep prefill
+  auto p = attn_params(a, kv, out, out, block_tables, seq_lens, B, G, scale);
+  TORCH_CHECK(G + 2 <= 16, a.op(), ": fused decode supports up to 14 q heads per kv head");
+  const VTail vt = v_tail_of(a, kv, v_tail, tail_slot, B);
+  p.v_tail = (__bf16*)vt.v_tail;
+  p.tail_slot = vt.tail_slot;
+  set_raw_qkv(a, p, qkv, B, positions, cos_sin, q_w, k_w, eps);
+  p.slots = a.ptr<int64_t>(slots, "slots", B);
   p.q_start = nullptr;
-  p.num_parts = num_parts;
-  p.part_size = part_size;
-  if (num_parts > 1) {
-    TORCH_CHECK(part_o.numel() >= (int64_t)B * p.Hkv * num_parts * G * 128,
-                "part_o workspace too small");
-    TORCH_CHECK(part_m.numel() >= (int64_t)B * p.Hkv * num_parts * G, "part_m too small");
-    p.part_m = part_m.data_ptr<float>();
-    p.part_l = part_l.data_ptr<float>();
-    p.part_o = part_o.data_ptr<float>();
-  }
-  const c10::DeviceGuard g(qkv.device());
+  set_split_kv(a, p, part_m, part_l, part_o, num_parts, part_size, B);
   akap::launch_paged_attn_decode(p, B, cur_stream());
 }
 
+// the tensors may have any dtype: the kernel only touches their bytes
 void l2_prefetch(std::vector<Tensor> ts, Tensor sink) {
-  TORCH_CHECK(ts.size() <= 8, "at most 8 tensors");
+  TORCH_CHECK(ts.size() <= 8, "l2_prefetch: at most 8 tensors");
+  const OpArgs a = on_gpu("l2_prefetch", sink, "sink");
   akap::PrefetchList L{};
   for (size_t i = 0; i < ts.size(); ++i) {
-    CHECK_GPU(ts[i]); CHECK_CONTIG(ts[i]);
-    L.ptr[i] = ts[i].data_ptr();
+    L.ptr[i] = a.ptr(ts[i], "ts[i]", {ts[i].scalar_type()});
     L.bytes[i] = (long)ts[i].numel() * ts[i].element_size();
   }
   L.n = ts.size();
-  const c10::DeviceGuard g(sink.device());
-  akap::launch_l2_prefetch(L, reinterpret_cast<uint32_t*>(sink.data_ptr<int>()), cur_stream());
+  akap::launch_l2_prefetch(L, reinterpret_cast<uint32_t*>(a.ptr<int>(sink, "sink", 1)),
+                           cur_stream());
 }
 
 int64_t gemm_splitk(int64_t M, int64_t N, int64_t K) {
@@ -329,27 +332,19 @@ int64_t gemm_splitk(int64_t M, int64_t N, int64_t K) {
 
 void gemm(Tensor out, Tensor x, Tensor w, Tensor ws, int64_t splitk,
           std::optional<Tensor> counters) {
-  CHECK_GPU(x); CHECK_BF16(x); CHECK_BF16(w); CHECK_BF16(out);
-  CHECK_LAST_CONTIG(x); CHECK_LAST_CONTIG(w); CHECK_LAST_CONTIG(out);
+  const OpArgs a = on_gpu("gemm", x, "x");
   TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && out.dim() == 2, "gemm: 2-D tensors");
   const int M = x.size(0), K = x.size(1), N = w.size(0);
   TORCH_CHECK(w.size(1) == K && out.size(0) == M && out.size(1) == N, "gemm: shape mismatch");
   TORCH_CHECK(K % 8 == 0 && N % 4 == 0, "gemm: K % 8, N % 4");
   TORCH_CHECK(x.stride(0) % 8 == 0 && w.stride(0) % 8 == 0, "gemm: 16-byte aligned rows");
-  if (splitk > 1) {
-    TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.numel() >= splitk * M * N,
-                "gemm: fp32 workspace of splitk*M*N");
-  }
-  int* cnt = nullptr;
-  if (counters && splitk > 1) {
-    TORCH_CHECK(counters->scalar_type() == at::kInt && counters->is_cuda(), "counters int32");
-    TORCH_CHECK(counters->numel() >= (int64_t)((M + 63) / 64) * ((N + 63) / 64) * akap::kCtrStride,
-                "counters: one L2 line (kCtrStride ints) per 64x64 tile");
-    cnt = counters->data_ptr<int>();
-  }
-  const c10::DeviceGuard g(x.device());
-  akap::launch_gemm_bf16(x.data_ptr(), w.data_ptr(), out.data_ptr(),
-                         splitk > 1 ? ws.data_ptr<float>() : nullptr, M, N, K, x.stride(0),
+  // split-K: fp32 workspace of splitk*M*N; counters: one L2 line (kCtrStride ints) per 64x64 tile
+  float* wsp = splitk > 1 ? a.ptr<float>(ws, "workspace", splitk * M * N) : nullptr;
+  int* cnt = splitk > 1 ? a.ptr<int>(counters, "counters",
+                                     (int64_t)((M + 63) / 64) * ((N + 63) / 64) * akap::kCtrStride)
+                        : nullptr;
+  akap::launch_gemm_bf16(a.bf16(x, "x", 0, kLastContig), a.bf16(w, "w", 0, kLastContig),
+                         a.bf16(out, "out", 0, kLastContig), wsp, M, N, K, x.stride(0),
                          w.stride(0), out.stride(0), splitk, cur_stream(), cnt);
 }
 
@@ -373,16 +368,14 @@ static int device_cus(int dev) {
 
 // The checks and DGemmArgs fields dgemm() and kgemm() share: bf16 GPU operands with aligned rows,
 // out / x / w pointers, sizes and strides, eps, the epilogue, the process-default weight policy
-// and K stagger, the optional ss_in row scale and the EPI_RESNORM operands.  `op` prefixes the
-// messages.
-static akap::DGemmArgs dgemm_args(const char* op, const Tensor& out, const Tensor& x,
+// and K stagger, the optional ss_in row scale and the EPI_RESNORM operands.
+static akap::DGemmArgs dgemm_args(const OpArgs& o, const Tensor& out, const Tensor& x,
                                   const Tensor& w, double eps, int64_t epi,
                                   const std::optional<Tensor>& ss_in,
                                   const std::optional<Tensor>& ss_out,
                                   const std::optional<Tensor>& aout,
                                   const std::optional<Tensor>& ln_out) {
-  CHECK_GPU(x); CHECK_BF16(x); CHECK_BF16(w); CHECK_BF16(out);
-  CHECK_LAST_CONTIG(x); CHECK_LAST_CONTIG(w); CHECK_LAST_CONTIG(out);
+  const char* op = o.op();
   TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && out.dim() == 2, op, ": 2-D tensors");
   const int M = x.size(0), N = w.size(0), K = w.size(1);
   TORCH_CHECK(x.stride(0) % 8 == 0 && w.stride(0) % 8 == 0 && out.stride(0) % 4 == 0,
@@ -390,28 +383,22 @@ static akap::DGemmArgs dgemm_args(const char* op, const Tensor& out, const Tenso
   akap::DGemmArgs a{};
   a.ntw = akap::weight_nt_default();
   a.stag = akap::gemm_stagger_default();
-  a.X = x.data_ptr();
-  a.W = w.data_ptr();
-  a.Y = out.data_ptr();
+  a.X = o.bf16(x, "x", 0, kLastContig);
+  a.W = o.bf16(w, "w", 0, kLastContig);
+  a.Y = o.bf16(out, "out", 0, kLastContig);
   a.M = M; a.N = N; a.K = K;
   a.ldx = x.stride(0); a.ldw = w.stride(0); a.ldy = out.stride(0);
   a.eps = (float)eps;
   a.epi = (int)epi;
-  if (ss_in) {
-    TORCH_CHECK(ss_in->scalar_type() == at::kFloat && ss_in->is_cuda() && ss_in->numel() >= M,
-                op, ": ss_in fp32 [M]");
-    a.ss_in = ss_in->data_ptr<float>();
-  }
+  a.ss_in = o.ptr<float>(ss_in, "ss_in", M);
   if (epi == akap::EPI_RESNORM) {
-    TORCH_CHECK(ss_out && aout && ln_out, op, " resnorm epilogue: ss_out, aout, ln_out");
-    TORCH_CHECK(ss_out->scalar_type() == at::kFloat && ss_out->numel() >= M, "ss_out fp32 [M]");
-    CHECK_BF16(*aout); CHECK_CONTIG(*aout); CHECK_BF16(*ln_out);
+    TORCH_CHECK(ss_out && aout && ln_out, op, ": resnorm epilogue needs ss_out, aout, ln_out");
     TORCH_CHECK(aout->numel() == (int64_t)M * N && ln_out->numel() == N,
-                op, " resnorm: aout [M, N], ln_out [N]");
-    TORCH_CHECK(out.stride(0) == N, op, " resnorm: residual must be dense");
-    a.ss_out = ss_out->data_ptr<float>();
-    a.Aout = aout->data_ptr();
-    a.ln_out = ln_out->data_ptr();
+                op, ": resnorm aout [M, N], ln_out [N]");
+    TORCH_CHECK(out.stride(0) == N, op, ": resnorm residual must be dense");
+    a.ss_out = o.ptr<float>(*ss_out, "ss_out", M);
+    a.Aout = o.bf16(*aout, "aout");
+    a.ln_out = o.bf16(*ln_out, "ln_out", N);
   }
   return a;
 }
@@ -423,8 +410,9 @@ void dgemm(Tensor out, Tensor x, Tensor w, Tensor ws, int64_t pro, int64_t split
            std::optional<Tensor> counters, int64_t bm) {
   TORCH_CHECK(pro >= 0 && pro <= 2, "dgemm: prologue 0|1|2");
   TORCH_CHECK(epi >= 0 && epi <= 2, "dgemm: epilogue 0|1|2");
+  const OpArgs o = on_gpu("dgemm", x, "x");
   // the ss_in row scale belongs to the plain prologue (the others have their own)
-  akap::DGemmArgs a = dgemm_args("dgemm", out, x, w, eps, epi,
+  akap::DGemmArgs a = dgemm_args(o, out, x, w, eps, epi,
                                  pro == akap::PRO_PLAIN ? ss_in : std::nullopt, ss_out, aout,
                                  ln_out);
   const int M = a.M, N = a.N, K = a.K;
@@ -438,35 +426,29 @@ void dgemm(Tensor out, Tensor x, Tensor w, Tensor ws, int64_t pro, int64_t split
                            (int)bm, counters.has_value(), device_cus(x.device().index()));
   TORCH_CHECK(c.supported, "dgemm: unsupported M/N/K/pro/epi/splitk/pf/bn/bm");
   if (splitk > 1) {
-    TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.numel() >= c.ws_floats,
-                "dgemm: fp32 workspace of splitk*M*N (+ splitk*M for the norm)");
+    // fp32 workspace of splitk*M*N (+ splitk*M for the norm)
+    a.ws = o.ptr<float>(ws, "workspace", c.ws_floats);
     TORCH_CHECK(out.stride(0) == N || c.inlaunch,
                 "dgemm: split-K output must be dense (separate reduce pass)");
   }
-  a.ws = splitk > 1 ? ws.data_ptr<float>() : nullptr;
   a.bn = (int)bn;
   a.ns = (int)ns;
   a.bm = (int)bm;
   if (c.ticket_ints > 0) {
-    // in-launch split-K combine: one zeroed int32 ticket per output tile
-    TORCH_CHECK(counters.has_value(), "dgemm bn=256: split-K needs the counters (2 per tile)");
-    TORCH_CHECK(counters->scalar_type() == at::kInt && counters->is_cuda() &&
-                    counters->numel() >= c.ticket_ints,
-                "dgemm: counters int32, one L2 line per output tile (bn=256: the kCtrInts array)");
-    a.counters = counters->data_ptr<int>();
+    // in-launch split-K combine: one zeroed int32 ticket per output tile, each on its own L2
+    // line (bn=256: 2 per tile, the kCtrInts array)
+    TORCH_CHECK(counters.has_value(), "dgemm: counters needed by the in-launch split-K combine");
+    a.counters = o.ptr<int>(*counters, "counters", c.ticket_ints);
   }
   if (pro == akap::PRO_ADDNORM) {
-    TORCH_CHECK(r && rout && ln, "dgemm addnorm: residual, residual-out and norm weight");
-    CHECK_BF16(*r); CHECK_BF16(*rout); CHECK_BF16(*ln);
-    CHECK_CONTIG(*r); CHECK_CONTIG(*rout); CHECK_CONTIG(*ln);
+    TORCH_CHECK(r && rout && ln, "dgemm: addnorm needs residual, residual-out and norm weight");
     TORCH_CHECK(r->numel() == (int64_t)M * K && rout->numel() == (int64_t)M * K &&
-                ln->numel() == K, "dgemm addnorm: residual [M, K], norm weight [K]");
-    TORCH_CHECK(r->data_ptr() != rout->data_ptr(), "dgemm addnorm: rout must not alias r");
-    a.R = r->data_ptr();
-    a.Rout = rout->data_ptr();
-    a.ln = ln->data_ptr();
+                ln->numel() == K, "dgemm: addnorm residual [M, K], norm weight [K]");
+    a.R = o.bf16(*r, "r");
+    a.Rout = o.bf16(*rout, "rout");
+    a.ln = o.bf16(*ln, "ln");
+    TORCH_CHECK(a.R != a.Rout, "dgemm: rout must not alias r");
   }
-  const c10::DeviceGuard g(x.device());
   if (c.family == akap::DG_PGEMM_SK) {
     akap::launch_pgemm_sk(a, (int)splitk, cur_stream());
     return;
@@ -477,66 +459,47 @@ void dgemm(Tensor out, Tensor x, Tensor w, Tensor ws, int64_t pro, int64_t split
 // Wide-row weight-streaming GEMM (LM head): out[M, N] = x[M, K] @ w[N, K]^T, one workgroup
 // per column tile holding all (<= 256) rows, so the weights cross HBM -> CU once.
 void wgemm(Tensor out, Tensor x, Tensor w) {
-  CHECK_GPU(x); CHECK_BF16(x); CHECK_BF16(w); CHECK_BF16(out);
-  CHECK_LAST_CONTIG(x); CHECK_LAST_CONTIG(w); CHECK_LAST_CONTIG(out);
+  const OpArgs o = on_gpu("wgemm", x, "x");
   TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && out.dim() == 2, "wgemm: 2-D tensors");
   const int M = x.size(0), N = w.size(0), K = w.size(1);
   TORCH_CHECK(x.size(1) == K && out.size(0) == M && out.size(1) == N, "wgemm: shapes");
   TORCH_CHECK(akap::wgemm_supported(M, N, K, x.stride(0), w.stride(0), out.stride(0)),
               "wgemm: K % 64 == 0 and 16-byte aligned rows");
-  akap::WGemmArgs a{x.data_ptr(), w.data_ptr(), out.data_ptr(), M, N, K,
+  akap::WGemmArgs a{o.bf16(x, "x", 0, kLastContig), o.bf16(w, "w", 0, kLastContig),
+                    o.bf16(out, "out", 0, kLastContig), M, N, K,
                     (int)x.stride(0), (int)w.stride(0), (int)out.stride(0)};
-  const c10::DeviceGuard g(x.device());
   akap::launch_wgemm(a, cur_stream());
 }
 
 // FP8-weight decode GEMM (csrc/kernels/qgemm.hip): out[M, N] = bf16(scale[n] * x[M, K] @
 // float(wq[N, K])^T), wq = OCP e4m3fn bytes (uint8 or float8_e4m3fn), scale fp32 per channel.
-bool is_fp8_bytes(const Tensor& t) {
-  return t.scalar_type() == at::kByte || t.scalar_type() == at::kFloat8_e4m3fn;
-}
-
 void qgemm(Tensor out, Tensor x, Tensor wq, Tensor scale) {
-  CHECK_GPU(x); CHECK_GPU(wq); CHECK_GPU(scale); CHECK_GPU(out);
-  CHECK_BF16(x); CHECK_BF16(out);
-  TORCH_CHECK(is_fp8_bytes(wq), "qgemm: wq must be uint8 / float8_e4m3fn (e4m3fn codes)");
-  TORCH_CHECK(scale.scalar_type() == at::kFloat, "qgemm: scale must be fp32");
+  const OpArgs o = on_gpu("qgemm", x, "x");
   TORCH_CHECK(x.dim() == 2 && wq.dim() == 2 && out.dim() == 2 && scale.dim() == 1,
               "qgemm: x, wq, out 2-D and scale 1-D");
-  CHECK_LAST_CONTIG(x); CHECK_LAST_CONTIG(out); CHECK_CONTIG(wq); CHECK_CONTIG(scale);
-  TORCH_CHECK(x.device() == wq.device() && x.device() == scale.device() &&
-              x.device() == out.device(), "qgemm: tensors on different devices");
   const int M = x.size(0), N = wq.size(0), K = wq.size(1);
   TORCH_CHECK(x.size(1) == K && out.size(0) == M && out.size(1) == N && scale.size(0) == N,
               "qgemm: shapes");
-  if (M == 0) return;
-  TORCH_CHECK(akap::qgemm_supported(M, N, K, x.stride(0), out.stride(0)),
+  TORCH_CHECK(M == 0 || akap::qgemm_supported(M, N, K, x.stride(0), out.stride(0)),
               "qgemm: needs M <= 256, K % 64 == 0, N % 8 == 0 and 16-byte aligned rows");
-  TORCH_CHECK((uintptr_t)x.data_ptr() % 16 == 0 && (uintptr_t)wq.data_ptr() % 16 == 0 &&
-              (uintptr_t)out.data_ptr() % 16 == 0 && (uintptr_t)scale.data_ptr() % 16 == 0,
-              "qgemm: 16-byte aligned base addresses");
-  akap::QGemmArgs a{x.data_ptr(), wq.data_ptr(), scale.data_ptr<float>(), out.data_ptr(),
+  akap::QGemmArgs a{o.bf16(x, "x", 0, kLastContig | kAlign16),
+                    o.ptr(wq, "wq", {at::kByte, at::kFloat8_e4m3fn}, 0, kContig | kAlign16),
+                    o.ptr<float>(scale, "scale", N, kContig | kAlign16),
+                    o.bf16(out, "out", 0, kLastContig | kAlign16),
                     M, N, K, (int)x.stride(0), (int)out.stride(0)};
-  const c10::DeviceGuard g(x.device());
   akap::launch_qgemm(a, cur_stream());
 }
 
 // out[N, K] bf16 = bf16(float(wq) * scale[:, None]) (one fp32 multiply, RNE cast)
 void dequant_fp8(Tensor out, Tensor wq, Tensor scale) {
-  CHECK_GPU(wq); CHECK_GPU(scale); CHECK_GPU(out); CHECK_BF16(out);
-  TORCH_CHECK(is_fp8_bytes(wq), "dequant_fp8: wq must be uint8 / float8_e4m3fn");
-  TORCH_CHECK(scale.scalar_type() == at::kFloat, "dequant_fp8: scale must be fp32");
+  const OpArgs o = on_gpu("dequant_fp8", wq, "wq");
   TORCH_CHECK(wq.dim() == 2 && out.dim() == 2 && scale.dim() == 1, "dequant_fp8: dims");
-  CHECK_CONTIG(wq); CHECK_CONTIG(out); CHECK_CONTIG(scale);
-  TORCH_CHECK(wq.device() == out.device() && wq.device() == scale.device(),
-              "dequant_fp8: tensors on different devices");
   const int64_t N = wq.size(0), K = wq.size(1);
   TORCH_CHECK(out.size(0) == N && out.size(1) == K && scale.size(0) == N, "dequant_fp8: shapes");
   TORCH_CHECK(K % 16 == 0, "dequant_fp8: K % 16 == 0");
-  TORCH_CHECK((uintptr_t)wq.data_ptr() % 16 == 0 && (uintptr_t)out.data_ptr() % 16 == 0,
-              "dequant_fp8: 16-byte aligned base addresses");
-  const c10::DeviceGuard g(wq.device());
-  akap::launch_dequant_fp8(wq.data_ptr(), scale.data_ptr<float>(), out.data_ptr(), N, (int)K,
+  const unsigned vec = kContig | kAlign16;
+  akap::launch_dequant_fp8(o.ptr(wq, "wq", {at::kByte, at::kFloat8_e4m3fn}, 0, vec),
+                           o.ptr<float>(scale, "scale", N), o.bf16(out, "out", 0, vec), N, (int)K,
                            cur_stream());
 }
 
@@ -547,149 +510,132 @@ void kgemm(Tensor out, Tensor x, Tensor w, int64_t bm, int64_t epi, double eps,
            std::optional<Tensor> ss_in, std::optional<Tensor> ss_out, std::optional<Tensor> aout,
            std::optional<Tensor> ln_out) {
   TORCH_CHECK(epi == 0 || epi == 1, "kgemm: epilogue 0|1");
-  const akap::DGemmArgs a = dgemm_args("kgemm", out, x, w, eps, epi, ss_in, ss_out, aout, ln_out);
+  const OpArgs o = on_gpu("kgemm", x, "x");
+  const akap::DGemmArgs a = dgemm_args(o, out, x, w, eps, epi, ss_in, ss_out, aout, ln_out);
   const int M = a.M, N = a.N, K = a.K;
   TORCH_CHECK(x.size(1) == K && out.size(0) == M && out.size(1) == N, "kgemm: shapes");
   TORCH_CHECK(akap::kgemm_supported(M, N, K, (int)bm, (int)epi), "kgemm: bm 16|32, N % 32, K % 256");
-  const c10::DeviceGuard g(x.device());
   akap::launch_kgemm(a, (int)bm, cur_stream());
+}
+
+// fp32 or bf16 logits [B, V] with unit last stride
+void* logits_of(const OpArgs& a, const Tensor& logits) {
+  TORCH_CHECK(logits.dim() == 2, a.op(), ": logits must be [B, V]");
+  return a.ptr(logits, "logits", {at::kFloat, at::kBFloat16}, 0, kLastContig);
 }
 
 void sample(Tensor logits, Tensor temperature, Tensor top_k, Tensor top_p, Tensor seeds,
             Tensor steps, Tensor out_tokens, Tensor out_logprobs, bool greedy_logprobs,
             Tensor ws, Tensor tickets, bool filtered) {
-  CHECK_GPU(logits);
-  TORCH_CHECK(logits.scalar_type() == at::kFloat || logits.scalar_type() == at::kBFloat16,
-              "sampler expects fp32 or bf16 logits");
-  CHECK_LAST_CONTIG(logits);
-  TORCH_CHECK(temperature.scalar_type() == at::kFloat && top_p.scalar_type() == at::kFloat,
-              "temperature/top_p fp32");
-  TORCH_CHECK(top_k.scalar_type() == at::kInt && steps.scalar_type() == at::kInt, "int32");
-  TORCH_CHECK(seeds.scalar_type() == at::kLong && out_tokens.scalar_type() == at::kLong, "int64");
+  const OpArgs a = on_gpu("sample", logits, "logits");
+  akap::SampleParams p{};
+  p.logits = logits_of(a, logits);
   const int B = logits.size(0);
   TORCH_CHECK(logits.size(1) >= 1 && logits.size(1) <= akap::kSampleMaxVocab,
-              "sampler rows: 1 .. ", akap::kSampleMaxVocab, " logits");
-  TORCH_CHECK(temperature.numel() >= B && top_k.numel() >= B && top_p.numel() >= B &&
-                  seeds.numel() >= B && steps.numel() >= B && out_tokens.numel() >= B &&
-                  (out_logprobs.numel() == 0 || out_logprobs.numel() >= B),
-              "sampler: one parameter / output entry per row");
-  akap::SampleParams p{};
-  p.logits = logits.data_ptr();
+              "sample: logits rows of 1 .. ", akap::kSampleMaxVocab, " entries");
   p.is_bf16 = logits.scalar_type() == at::kBFloat16;
   p.ld = logits.stride(0);
   p.V = logits.size(1);
-  p.temperature = temperature.data_ptr<float>();
-  p.top_k = top_k.data_ptr<int>();
-  p.top_p = top_p.data_ptr<float>();
-  p.seeds = seeds.data_ptr<int64_t>();
-  p.steps = steps.data_ptr<int>();
-  p.out_tokens = out_tokens.data_ptr<int64_t>();
-  p.out_logprobs = out_logprobs.numel() ? out_logprobs.data_ptr<float>() : nullptr;
+  // one parameter / output entry per row
+  p.temperature = a.ptr<float>(temperature, "temperature", B);
+  p.top_k = a.ptr<int>(top_k, "top_k", B);
+  p.top_p = a.ptr<float>(top_p, "top_p", B);
+  p.seeds = a.ptr<int64_t>(seeds, "seeds", B);
+  p.steps = a.ptr<int>(steps, "steps", B);
+  p.out_tokens = a.ptr<int64_t>(out_tokens, "out_tokens", B);
+  p.out_logprobs = a.ptr_unless_empty<float>(out_logprobs, "out_logprobs", B);
   p.greedy_logprobs = greedy_logprobs ? 1 : 0;
-  // workspace: per-(row, chunk) 32-byte partial records + one ticket per row (ops.sample keeps
-  // both persistent; the tickets are zeroed once and re-armed by each row's last chunk)
-  CHECK_GPU(ws); CHECK_CONTIG(ws); CHECK_GPU(tickets); CHECK_CONTIG(tickets);
-  TORCH_CHECK(ws.scalar_type() == at::kFloat && tickets.scalar_type() == at::kInt,
-              "sampler workspace fp32, tickets int32");
-  TORCH_CHECK(ws.numel() >= (int64_t)akap::sample_ws_floats(B),
-              "sampler workspace too small (chunk records + filter-pass states / histograms)");
-  TORCH_CHECK(tickets.numel() >= (int64_t)B * akap::kCtrStride,
-              "one ticket per row, each on its own L2 line (kCtrStride ints)");
-  const c10::DeviceGuard g(logits.device());
-  akap::launch_sample(p, B, ws.data_ptr(), tickets.data_ptr<int>(), filtered ? 1 : 0,
-                      cur_stream());
+  // workspace: per-(row, chunk) 32-byte partial records + filter-pass states / histograms, and
+  // one ticket per row, each on its own L2 line (ops.sample keeps both persistent; the tickets
+  // are zeroed once and re-armed by each row's last chunk)
+  akap::launch_sample(p, B, a.ptr<float>(ws, "workspace", (int64_t)akap::sample_ws_floats(B)),
+                      a.ptr<int>(tickets, "tickets", (int64_t)B * akap::kCtrStride),
+                      filtered ? 1 : 0, cur_stream());
 }
 
+// presence / frequency / repetition are indexed by the row numbers in `rows`, which only the
+// device knows: the engine sizes them by its sampled rows, so the host can only ask that the
+// three are equally long
 void apply_penalties(Tensor logits, Tensor rows, Tensor toks, Tensor counts, Tensor presence,
                      Tensor frequency, Tensor repetition) {
-  CHECK_GPU(logits); CHECK_LAST_CONTIG(logits);
-  TORCH_CHECK(logits.scalar_type() == at::kFloat || logits.scalar_type() == at::kBFloat16,
-              "fp32 or bf16 logits");
-  TORCH_CHECK(rows.scalar_type() == at::kInt && toks.scalar_type() == at::kInt &&
-                  counts.scalar_type() == at::kInt, "rows/toks/counts int32");
-  TORCH_CHECK(presence.scalar_type() == at::kFloat && frequency.scalar_type() == at::kFloat &&
-                  repetition.scalar_type() == at::kFloat, "penalties fp32");
+  const OpArgs a = on_gpu("apply_penalties", logits, "logits");
   const int n = rows.numel();
-  TORCH_CHECK(toks.numel() == n && counts.numel() == n, "COO length mismatch");
-  const c10::DeviceGuard g(logits.device());
-  akap::launch_apply_penalties(logits.data_ptr(), logits.stride(0),
-                               logits.scalar_type() == at::kBFloat16, rows.data_ptr<int>(),
-                               toks.data_ptr<int>(), counts.data_ptr<int>(),
-                               presence.data_ptr<float>(), frequency.data_ptr<float>(),
-                               repetition.data_ptr<float>(), n, cur_stream());
+  TORCH_CHECK(toks.numel() == n && counts.numel() == n, "apply_penalties: COO length mismatch");
+  const int64_t np = n ? std::max<int64_t>(presence.numel(), 1) : 0;
+  akap::launch_apply_penalties(logits_of(a, logits), logits.stride(0),
+                               logits.scalar_type() == at::kBFloat16, a.ptr<int>(rows, "rows"),
+                               a.ptr<int>(toks, "toks", n), a.ptr<int>(counts, "counts", n),
+                               a.ptr<float>(presence, "presence", np),
+                               a.ptr<float>(frequency, "frequency", np),
+                               a.ptr<float>(repetition, "repetition", np), n, cur_stream());
 }
 
 void argmax(Tensor logits, Tensor out) {
-  CHECK_GPU(logits); CHECK_LAST_CONTIG(logits);
-  TORCH_CHECK(logits.scalar_type() == at::kBFloat16 || logits.scalar_type() == at::kFloat,
-              "argmax expects bf16/fp32");
-  TORCH_CHECK(out.scalar_type() == at::kLong, "out int64");
-  const c10::DeviceGuard g(logits.device());
-  akap::launch_argmax(logits.data_ptr(), logits.stride(0), logits.size(1),
-                      logits.scalar_type() == at::kBFloat16, out.data_ptr<int64_t>(),
-                      logits.size(0), cur_stream());
+  const OpArgs a = on_gpu("argmax", logits, "logits");
+  akap::launch_argmax(logits_of(a, logits), logits.stride(0), logits.size(1),
+                      logits.scalar_type() == at::kBFloat16,
+                      a.ptr<int64_t>(out, "out", logits.size(0)), logits.size(0), cur_stream());
 }
 
 void moe_topk_softmax(Tensor logits, Tensor topk_w, Tensor topk_ids, bool renorm) {
-  CHECK_GPU(logits); CHECK_BF16(logits); CHECK_LAST_CONTIG(logits);
-  TORCH_CHECK(logits.size(1) <= 256, "at most 256 experts");
+  const OpArgs a = on_gpu("moe_topk_softmax", logits, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.size(1) <= 256, "moe_topk_softmax: at most 256 experts");
   TORCH_CHECK(topk_w.size(1) >= 1 && topk_w.size(1) <= 8 && topk_w.size(1) <= logits.size(1),
-              "top-k in 1..min(8, E)");
+              "moe_topk_softmax: top-k in 1..min(8, E)");
   TORCH_CHECK(topk_ids.sizes() == topk_w.sizes() && topk_w.size(0) == logits.size(0),
-              "topk_w / topk_ids [T, K]");
-  const c10::DeviceGuard g(logits.device());
-  akap::launch_moe_topk_softmax(logits.data_ptr(), logits.stride(0), logits.size(1),
-                                topk_w.size(1), topk_w.data_ptr<float>(),
-                                topk_ids.data_ptr<int32_t>(), logits.size(0), renorm ? 1 : 0,
-                                cur_stream());
+              "moe_topk_softmax: topk_w / topk_ids [T, K]");
+  akap::launch_moe_topk_softmax(a.bf16(logits, "logits", 0, kLastContig), logits.stride(0),
+                                logits.size(1), topk_w.size(1), a.ptr<float>(topk_w, "topk_w"),
+                                a.ptr<int32_t>(topk_ids, "topk_ids"), logits.size(0),
+                                renorm ? 1 : 0, cur_stream());
 }
 
 void moe_router_topk(Tensor h, Tensor router, Tensor topk_w, Tensor topk_ids, bool renorm) {
-  CHECK_GPU(h); CHECK_BF16(h); CHECK_LAST_CONTIG(h);
-  CHECK_GPU(router); CHECK_BF16(router); CHECK_CONTIG(router);
-  const int d = h.size(1), E = router.size(0);
-  TORCH_CHECK(router.size(1) == d, "router shape");
-  TORCH_CHECK(akap::moe_router_topk_supported(E, d), "fused router supports <= 16 experts, d % 8 == 0");
-  TORCH_CHECK(topk_w.size(0) >= h.size(0) && topk_ids.size(0) >= h.size(0), "outputs too small");
-  TORCH_CHECK(((uintptr_t)h.data_ptr() % 16) == 0 && h.stride(0) % 8 == 0, "h rows 16-B aligned");
-  const c10::DeviceGuard g(h.device());
-  akap::launch_moe_router_topk(h.data_ptr(), h.stride(0), router.data_ptr(), d, E, topk_w.size(1),
-                               topk_w.data_ptr<float>(), topk_ids.data_ptr<int32_t>(), h.size(0),
+  const OpArgs a = on_gpu("moe_router_topk", h, "h");
+  TORCH_CHECK(h.dim() == 2 && router.dim() == 2 && topk_w.dim() == 2, "moe_router_topk: 2-D");
+  const int T = h.size(0), d = h.size(1), E = router.size(0), K = topk_w.size(1);
+  TORCH_CHECK(router.size(1) == d, "moe_router_topk: router shape");
+  TORCH_CHECK(akap::moe_router_topk_supported(E, d),
+              "moe_router_topk: the fused router supports <= 16 experts, d % 8 == 0");
+  TORCH_CHECK(topk_w.size(0) >= T && topk_ids.size(0) >= T, "moe_router_topk: outputs too small");
+  TORCH_CHECK(h.stride(0) % 8 == 0, "moe_router_topk: h rows must be 16-byte aligned");
+  akap::launch_moe_router_topk(a.bf16(h, "h", 0, kLastContig | kAlign16), h.stride(0),
+                               a.bf16(router, "router"), d, E, K,
+                               a.ptr<float>(topk_w, "topk_w", (int64_t)T * K),
+                               a.ptr<int32_t>(topk_ids, "topk_ids", (int64_t)T * K), T,
                                renorm ? 1 : 0, cur_stream());
 }
 
 void moe_align(Tensor topk_ids, int64_t E, int64_t block, Tensor sorted_ids, Tensor offsets,
                Tensor num_padded, Tensor inv, Tensor tile_expert) {
-  CHECK_GPU(topk_ids); CHECK_CONTIG(topk_ids);
+  const OpArgs a = on_gpu("moe_align", topk_ids, "topk_ids");
   const int n = topk_ids.numel();
-  TORCH_CHECK(sorted_ids.numel() >= n + E * (block - 1), "sorted_ids too small");
-  TORCH_CHECK(inv.numel() == 0 || inv.numel() >= n, "inv too small");
   const int max_tiles = tile_expert.numel();
   TORCH_CHECK(max_tiles == 0 || (int64_t)max_tiles * block >= sorted_ids.numel(),
-              "tile_expert must cover sorted_ids");
-  const c10::DeviceGuard g(topk_ids.device());
-  akap::launch_moe_align(topk_ids.data_ptr<int32_t>(), n, E, block,
-                         sorted_ids.data_ptr<int32_t>(), offsets.data_ptr<int32_t>(),
-                         num_padded.data_ptr<int32_t>(),
-                         inv.numel() ? inv.data_ptr<int32_t>() : nullptr,
-                         max_tiles ? tile_expert.data_ptr<int32_t>() : nullptr, max_tiles,
+              "moe_align: tile_expert must cover sorted_ids");
+  akap::launch_moe_align(a.ptr<int32_t>(topk_ids, "topk_ids"), n, E, block,
+                         a.ptr<int32_t>(sorted_ids, "sorted_ids", n + E * (block - 1)),
+                         a.ptr<int32_t>(offsets, "offsets", E + 1),
+                         a.ptr<int32_t>(num_padded, "num_padded", 1),
+                         a.ptr_unless_empty<int32_t>(inv, "inv", n),
+                         a.ptr_unless_empty<int32_t>(tile_expert, "tile_expert"), max_tiles,
                          cur_stream());
 }
 
 void moe_gemm(Tensor out, Tensor a, Tensor w, Tensor sorted_ids, Tensor tile_expert,
               int64_t n_flat, int64_t topk, bool gather) {
-  CHECK_GPU(a); CHECK_BF16(a); CHECK_BF16(w); CHECK_CONTIG(w); CHECK_CONTIG(out);
-  CHECK_LAST_CONTIG(a);
-  TORCH_CHECK(w.dim() == 3, "expert weights [E, N, K]");
+  const OpArgs o = on_gpu("moe_gemm", a, "a");
+  TORCH_CHECK(w.dim() == 3 && a.dim() == 2 && out.dim() == 2, "moe_gemm: expert weights [E, N, K]");
   const int N = w.size(1), K = w.size(2);
-  TORCH_CHECK(a.size(1) == K && out.size(1) == N, "moe_gemm shape mismatch");
-  TORCH_CHECK(K % 8 == 0, "K % 8");
+  TORCH_CHECK(a.size(1) == K && out.size(1) == N, "moe_gemm: shape mismatch");
+  TORCH_CHECK(K % 8 == 0, "moe_gemm: K % 8");
   const int max_tiles = tile_expert.numel();
-  TORCH_CHECK(out.size(0) >= (int64_t)max_tiles * 64, "out rows must cover all tiles");
-  if (!gather) TORCH_CHECK(a.size(0) >= (int64_t)max_tiles * 64, "a rows must cover all tiles");
-  const c10::DeviceGuard g(a.device());
-  akap::launch_moe_gemm(a.data_ptr(), w.data_ptr(), out.data_ptr(), sorted_ids.data_ptr<int32_t>(),
-                        tile_expert.data_ptr<int32_t>(), max_tiles, n_flat, topk, N, K,
+  const int64_t rows = (int64_t)max_tiles * 64;
+  TORCH_CHECK(out.size(0) >= rows, "moe_gemm: out rows must cover all tiles");
+  TORCH_CHECK(gather || a.size(0) >= rows, "moe_gemm: a rows must cover all tiles");
+  akap::launch_moe_gemm(o.bf16(a, "a", 0, kLastContig), o.bf16(w, "w"), o.bf16(out, "out"),
+                        o.ptr<int32_t>(sorted_ids, "sorted_ids"),  // read for live tiles only
+                        o.ptr<int32_t>(tile_expert, "tile_expert"), max_tiles, n_flat, topk, N, K,
                         a.stride(0), gather ? 1 : 0, cur_stream());
 }
 
@@ -698,28 +644,22 @@ void moe_gemm(Tensor out, Tensor a, Tensor w, Tensor sorted_ids, Tensor tile_exp
 void moe_dgemm(Tensor out, Tensor a, Tensor w, Tensor sorted_ids, Tensor tile_expert,
                int64_t n_flat, int64_t topk, bool gather, bool silu, int64_t pf, int64_t bm,
                int64_t splitk) {
-  CHECK_GPU(a); CHECK_BF16(a); CHECK_BF16(w); CHECK_CONTIG(w); CHECK_CONTIG(out);
-  CHECK_LAST_CONTIG(a);
-  TORCH_CHECK(w.dim() == 3, "expert weights [E, N, K]");
+  const OpArgs o = on_gpu("moe_dgemm", a, "a");
+  TORCH_CHECK(w.dim() == 3 && a.dim() == 2, "moe_dgemm: a [rows, K], expert weights [E, N, K]");
   const int N = w.size(1), K = w.size(2);
   TORCH_CHECK(a.size(1) == K, "moe_dgemm: a width != K");
   TORCH_CHECK(akap::moe_dgemm_supported(N, K, pf, silu, splitk), "moe_dgemm: unsupported N/K/pf/split");
   TORCH_CHECK(a.stride(0) % 8 == 0, "moe_dgemm: 16-byte aligned rows");
-  TORCH_CHECK(sorted_ids.scalar_type() == at::kInt && tile_expert.scalar_type() == at::kInt,
-              "moe_dgemm: int32 index tensors");
   TORCH_CHECK(bm == 32 || bm == 64, "moe_dgemm: tile rows 32 | 64");
   const int max_tiles = tile_expert.numel();
   const int64_t rows = (int64_t)max_tiles * bm;
-  if (splitk > 1) {
-    TORCH_CHECK(out.scalar_type() == at::kFloat && out.numel() >= splitk * rows * N,
-                "moe_dgemm: fp32 partials [splitk, rows, N]");
-  } else {
-    CHECK_BF16(out);
-    TORCH_CHECK(out.size(1) == (silu ? N / 2 : N), "moe_dgemm: out width");
-    TORCH_CHECK(out.size(0) >= rows, "moe_dgemm: out rows must cover all tiles");
-  }
-  TORCH_CHECK(sorted_ids.numel() >= rows, "moe_dgemm: sorted_ids too short");
-  if (!gather) TORCH_CHECK(a.size(0) >= rows, "moe_dgemm: a rows must cover all tiles");
+  // split-K: out is the fp32 partials [splitk, rows, N]
+  float* partials = splitk > 1 ? o.ptr<float>(out, "out", splitk * rows * N) : nullptr;
+  void* y = splitk > 1 ? nullptr : o.bf16(out, "out");
+  TORCH_CHECK(splitk > 1 || (out.dim() == 2 && out.size(1) == (silu ? N / 2 : N)),
+              "moe_dgemm: out width");
+  TORCH_CHECK(splitk > 1 || out.size(0) >= rows, "moe_dgemm: out rows must cover all tiles");
+  TORCH_CHECK(gather || a.size(0) >= rows, "moe_dgemm: a rows must cover all tiles");
   // Non-temporal expert-weight loads when each expert's weights are streamed by one row tile
   // (64-row tiles, <= 40 rows per expert on average): measured on MI355X, Mixtral T=128,
   // w13 345 -> 319 us, w2 (split 4) 226 -> 215 us; with 32-row tiles an expert's second tile
@@ -730,64 +670,59 @@ void moe_dgemm(Tensor out, Tensor a, Tensor w, Tensor sorted_ids, Tensor tile_ex
     return e ? std::atoi(e) : -1;
   }();
   const bool ntw = nt_env >= 0 ? nt_env != 0 : (bm == 64 && n_flat <= 40 * w.size(0));
-  const c10::DeviceGuard g(a.device());
-  akap::launch_moe_dgemm(a.data_ptr(), w.data_ptr(), splitk > 1 ? nullptr : out.data_ptr(),
-                         sorted_ids.data_ptr<int32_t>(), tile_expert.data_ptr<int32_t>(),
-                         max_tiles, n_flat, topk, N, K, a.stride(0),
-                         splitk > 1 ? N : out.stride(0), gather ? 1 : 0, silu ? 1 : 0, (int)pf,
-                         (int)bm, (int)splitk, splitk > 1 ? out.data_ptr<float>() : nullptr, ntw,
+  akap::launch_moe_dgemm(o.bf16(a, "a", 0, kLastContig), o.bf16(w, "w"), y,
+                         o.ptr<int32_t>(sorted_ids, "sorted_ids", rows),
+                         o.ptr<int32_t>(tile_expert, "tile_expert"), max_tiles, n_flat, topk, N,
+                         K, a.stride(0), splitk > 1 ? N : out.stride(0), gather ? 1 : 0,
+                         silu ? 1 : 0, (int)pf, (int)bm, (int)splitk, partials, ntw,
                          cur_stream());
 }
 
 void moe_combine_split(Tensor partials, Tensor wts, Tensor inv, Tensor out, int64_t splitk,
                        int64_t rows) {
-  CHECK_GPU(partials); CHECK_CONTIG(partials); CHECK_CONTIG(out); CHECK_BF16(out);
-  TORCH_CHECK(partials.scalar_type() == at::kFloat, "partials fp32");
-  TORCH_CHECK(wts.scalar_type() == at::kFloat && inv.scalar_type() == at::kInt, "dtypes");
+  const OpArgs a = on_gpu("moe_combine_split", partials, "partials");
+  TORCH_CHECK(out.dim() == 2 && wts.dim() == 2, "moe_combine_split: out [T, d], wts [T, topk]");
   const int T = out.size(0), d = out.size(1), topk = wts.size(1);
-  TORCH_CHECK(d % 8 == 0, "d % 8");
-  TORCH_CHECK(partials.numel() >= splitk * rows * d, "partials [splitk, rows, d]");
-  const c10::DeviceGuard g(out.device());
-  akap::launch_moe_combine_split(partials.data_ptr<float>(), wts.data_ptr<float>(),
-                                 inv.data_ptr<int32_t>(), out.data_ptr(), T, topk, d,
-                                 (int)splitk, (int)rows, cur_stream());
+  TORCH_CHECK(d % 8 == 0, "moe_combine_split: d % 8");
+  akap::launch_moe_combine_split(a.ptr<float>(partials, "partials", splitk * rows * d),
+                                 a.ptr<float>(wts, "wts", (int64_t)T * topk),
+                                 a.ptr<int32_t>(inv, "inv", (int64_t)T * topk),
+                                 a.bf16(out, "out"), T, topk, d, (int)splitk, (int)rows,
+                                 cur_stream());
 }
 
 void moe_combine(Tensor y, Tensor wts, Tensor inv, Tensor out) {
-  CHECK_GPU(y); CHECK_BF16(y); CHECK_CONTIG(y); CHECK_CONTIG(out);
-  TORCH_CHECK(wts.scalar_type() == at::kFloat && inv.scalar_type() == at::kInt, "dtypes");
+  const OpArgs a = on_gpu("moe_combine", y, "y");
+  TORCH_CHECK(out.dim() == 2 && wts.dim() == 2, "moe_combine: out [T, d], wts [T, topk]");
   const int T = out.size(0), d = out.size(1), topk = wts.size(1);
-  TORCH_CHECK(d % 8 == 0, "d % 8");
-  const c10::DeviceGuard g(y.device());
-  akap::launch_moe_combine(y.data_ptr(), wts.data_ptr<float>(), inv.data_ptr<int32_t>(),
-                           out.data_ptr(), T, topk, d, cur_stream());
+  TORCH_CHECK(d % 8 == 0, "moe_combine: d % 8");
+  akap::launch_moe_combine(a.bf16(y, "y"), a.ptr<float>(wts, "wts", (int64_t)T * topk),
+                           a.ptr<int32_t>(inv, "inv", (int64_t)T * topk), a.bf16(out, "out"), T,
+                           topk, d, cur_stream());
 }
 
+// cache: [planes, NB, ...block...]; out / buf: [planes, nblk, block].  The blocks move as raw
+// 16-byte vectors, so no dtype is asked of either.
 void kv_gather(Tensor cache, Tensor block_ids, Tensor out) {
-  // cache: [planes, NB, ...block...]
-  CHECK_GPU(cache); CHECK_CONTIG(cache); CHECK_CONTIG(out);
-  const int planes = cache.size(0);
-  const long plane_stride = cache.stride(0);
+  const OpArgs a = on_gpu("kv_gather", cache, "cache");
+  const int planes = cache.size(0), nblk = block_ids.numel();
   const int block_elems = cache.stride(1);
-  TORCH_CHECK(block_elems % 2048 == 0 || block_elems % 8 == 0, "block must be 16B multiple");
-  TORCH_CHECK(out.numel() >= (int64_t)planes * block_ids.numel() * block_elems, "out too small");
-  const c10::DeviceGuard g(cache.device());
-  TORCH_CHECK(block_ids.is_cuda() && block_ids.scalar_type() == at::kInt, "int32 GPU block ids");
-  akap::launch_kv_gather(cache.data_ptr(), plane_stride, planes, block_elems, cache.size(1),
-                         block_ids.data_ptr<int>(), block_ids.numel(), out.data_ptr(),
+  TORCH_CHECK(block_elems % 8 == 0, "kv_gather: a block must be a multiple of 16 bytes");
+  akap::launch_kv_gather(a.ptr(cache, "cache", {cache.scalar_type()}), cache.stride(0), planes,
+                         block_elems, cache.size(1), a.ptr<int>(block_ids, "block_ids"), nblk,
+                         a.ptr(out, "out", {out.scalar_type()},
+                               (int64_t)planes * nblk * block_elems),
                          cur_stream());
 }
 
 void kv_scatter(Tensor buf, Tensor cache, Tensor block_ids) {
-  CHECK_GPU(cache); CHECK_CONTIG(cache); CHECK_CONTIG(buf);
-  const int planes = cache.size(0);
-  const c10::DeviceGuard g(cache.device());
-  TORCH_CHECK(block_ids.is_cuda() && block_ids.scalar_type() == at::kInt, "int32 GPU block ids");
-  TORCH_CHECK(buf.numel() >= (int64_t)planes * block_ids.numel() * cache.stride(1),
-              "buf too small");
-  akap::launch_kv_scatter(buf.data_ptr(), cache.data_ptr(), cache.stride(0), planes,
-                          cache.stride(1), cache.size(1), block_ids.data_ptr<int>(),
-                          block_ids.numel(), cur_stream());
+  const OpArgs a = on_gpu("kv_scatter", cache, "cache");
+  const int planes = cache.size(0), nblk = block_ids.numel();
+  akap::launch_kv_scatter(a.ptr(buf, "buf", {buf.scalar_type()},
+                                (int64_t)planes * nblk * cache.stride(1)),
+                          a.ptr(cache, "cache", {cache.scalar_type()}), cache.stride(0), planes,
+                          cache.stride(1), cache.size(1), a.ptr<int>(block_ids, "block_ids"),
+                          nblk, cur_stream());
 }
 
 // hipIpc KV pull (see kv_transfer.hip).  src_planes / dst_planes: int64 device tables of
@@ -798,17 +733,13 @@ void kv_scatter(Tensor buf, Tensor cache, Tensor block_ids) {
 void kv_pull(Tensor src_planes, Tensor dst_planes, int64_t block_elems, Tensor pairs,
              std::optional<Tensor> tail, std::optional<Tensor> tail_jobs, int64_t Hkv,
              int64_t BS, int64_t D) {
-  TORCH_CHECK(src_planes.scalar_type() == at::kLong && src_planes.is_cuda() &&
-                  src_planes.is_contiguous() && dst_planes.scalar_type() == at::kLong &&
-                  dst_planes.is_cuda() && dst_planes.is_contiguous() &&
-                  src_planes.numel() == dst_planes.numel() && src_planes.numel() % 2 == 0,
-              "plane tables: int64 [2L] on the device, same length");
-  TORCH_CHECK(pairs.scalar_type() == at::kInt && pairs.is_cuda() && pairs.is_contiguous(),
-              "pairs int32 [n, 2] on the device");
-  TORCH_CHECK(pairs.numel() % 2 == 0, "pairs [n, 2]");
+  const OpArgs o = on_gpu("kv_pull", dst_planes, "dst_planes");
+  TORCH_CHECK(src_planes.numel() == dst_planes.numel() && src_planes.numel() % 2 == 0,
+              "kv_pull: plane tables int64 [2L], same length");
+  TORCH_CHECK(pairs.numel() % 2 == 0, "kv_pull: pairs [n, 2]");
   akap::KVPullArgs a{};
-  a.src_planes = src_planes.data_ptr<int64_t>();
-  a.dst_planes = dst_planes.data_ptr<int64_t>();
+  a.src_planes = o.ptr<int64_t>(src_planes, "src_planes");
+  a.dst_planes = o.ptr<int64_t>(dst_planes, "dst_planes");
   a.planes = src_planes.numel();
   a.block_elems = (int)block_elems;
   // bf16 cache: block = Hkv*BS*D; an fp8 (byte) cache is moved as bf16 pairs, block =
@@ -816,24 +747,21 @@ void kv_pull(Tensor src_planes, Tensor dst_planes, int64_t block_elems, Tensor p
   const bool byte_cache = (int64_t)a.block_elems * 2 == Hkv * BS * D;
   TORCH_CHECK(a.block_elems % 8 == 0 && (a.block_elems == Hkv * BS * D || byte_cache),
               "block = Hkv*BS*D (bf16) or Hkv*BS*D/2 (fp8 bytes viewed as bf16)");
-  a.pairs = pairs.data_ptr<int>();
+  a.pairs = o.ptr<int>(pairs, "pairs");
   a.nblk = pairs.numel() / 2;
   a.Hkv = Hkv; a.BS = BS; a.D = D;
   a.layers = a.planes / 2;
   if (tail && tail_jobs && tail_jobs->numel()) {
-    TORCH_CHECK(!byte_cache, "V-tail jobs need a bf16 cache");
-    CHECK_CONTIG((*tail)); CHECK_BF16((*tail));
+    TORCH_CHECK(!byte_cache, "kv_pull: V-tail jobs need a bf16 cache");
     TORCH_CHECK(tail->dim() == 5 && tail->size(0) == a.layers && tail->size(2) == Hkv &&
-                tail->size(3) == 8 && tail->size(4) == D, "tail [L, slots, Hkv, 8, D]");
-    TORCH_CHECK(tail_jobs->scalar_type() == at::kInt && tail_jobs->is_cuda() &&
-                tail_jobs->is_contiguous() && tail_jobs->numel() % 4 == 0, "tail_jobs [m, 4]");
-    TORCH_CHECK(BS % 8 == 0, "block size % 8");
-    a.tail = reinterpret_cast<__bf16*>(tail->data_ptr());
+                tail->size(3) == 8 && tail->size(4) == D, "kv_pull: tail [L, slots, Hkv, 8, D]");
+    TORCH_CHECK(tail_jobs->numel() % 4 == 0, "kv_pull: tail_jobs [m, 4]");
+    TORCH_CHECK(BS % 8 == 0, "kv_pull: block size % 8");
+    a.tail = reinterpret_cast<__bf16*>(o.bf16(*tail, "tail"));
     a.tail_slots = tail->size(1);
-    a.tail_jobs = tail_jobs->data_ptr<int>();
+    a.tail_jobs = o.ptr<int>(*tail_jobs, "tail_jobs");
     a.ntail = tail_jobs->numel() / 4;
   }
-  const c10::DeviceGuard g(dst_planes.device());
   akap::launch_kv_pull(a, cur_stream());
 }
 
@@ -841,79 +769,71 @@ void kv_pull(Tensor src_planes, Tensor dst_planes, int64_t block_elems, Tensor p
 // [gate; up] halves of w (epi 2, out [M, N/2]).  offs (int32 [G], device) -> expert-grouped:
 // rows of x sorted by group, w [G, N, K].
 void pgemm(Tensor out, Tensor x, Tensor w, int64_t epi, std::optional<Tensor> offs) {
-  CHECK_GPU(x); CHECK_BF16(x); CHECK_BF16(w); CHECK_BF16(out);
-  CHECK_LAST_CONTIG(x); CHECK_CONTIG(w); CHECK_LAST_CONTIG(out);
-  TORCH_CHECK(x.dim() == 2 && out.dim() == 2, "x, out must be 2-D");
-  TORCH_CHECK(epi == akap::EPI_STORE || epi == akap::EPI_SILU, "pgemm epilogue: store | silu");
+  const OpArgs o = on_gpu("pgemm", x, "x");
+  TORCH_CHECK(x.dim() == 2 && out.dim() == 2, "pgemm: x, out must be 2-D");
+  TORCH_CHECK(epi == akap::EPI_STORE || epi == akap::EPI_SILU, "pgemm: epilogue store | silu");
   akap::PGemmArgs a{};
   a.M = x.size(0);
   a.K = x.size(1);
   a.N = w.size(-2);
-  TORCH_CHECK(w.size(-1) == a.K, "w [.., N, K] must match x [M, K]");
+  TORCH_CHECK(w.size(-1) == a.K, "pgemm: w [.., N, K] must match x [M, K]");
   TORCH_CHECK(akap::pgemm_supported(a.M, a.N, a.K, x.stride(0)),
               "pgemm: N % 256 == 0 and K % 64 == 0 needed, X and each weight matrix below 2 GiB");
   TORCH_CHECK(out.size(0) == a.M && out.size(1) == (epi == akap::EPI_SILU ? a.N / 2 : a.N),
-              "out shape");
-  if (offs) {
-    TORCH_CHECK(w.dim() == 3 && offs->scalar_type() == at::kInt && offs->is_cuda() &&
-                    offs->numel() == w.size(0),
-                "grouped pgemm: w [G, N, K], offs int32 [G] on the device");
-    a.offs = offs->data_ptr<int>();
-    a.groups = offs->numel();
-  } else {
-    TORCH_CHECK(w.dim() == 2, "dense pgemm: w [N, K]");
-  }
-  a.X = x.data_ptr();
-  a.W = w.data_ptr();
-  a.Y = out.data_ptr();
+              "pgemm: out shape");
+  // grouped: w [G, N, K] with offs int32 [G]; dense: w [N, K]
+  TORCH_CHECK(w.dim() == (offs ? 3 : 2) && (!offs || offs->numel() == w.size(0)),
+              "pgemm: w [N, K], or w [G, N, K] with offs [G]");
+  a.offs = o.ptr<int>(offs, "offs");
+  a.groups = offs ? offs->numel() : 0;
+  a.X = o.bf16(x, "x", 0, kLastContig);
+  a.W = o.bf16(w, "w");
+  a.Y = o.bf16(out, "out", 0, kLastContig);
   a.ldx = x.stride(0);
   a.ldy = out.stride(0);
-  TORCH_CHECK(a.ldx % 8 == 0 && a.ldy % 4 == 0, "row strides must keep 16-B / 8-B alignment");
-  const c10::DeviceGuard g(x.device());
+  TORCH_CHECK(a.ldx % 8 == 0 && a.ldy % 4 == 0,
+              "pgemm: row strides must keep 16-B / 8-B alignment");
   akap::launch_pgemm(a, (int)epi, cur_stream());
 }
 
 // dst (device) <- src (pinned host) by a kernel that reads the device mapping of the host
 // buffer (no hipMemcpyAsync): the caller keeps src untouched until the stream passes it
 void h2d_stage(Tensor dst, Tensor src) {
-  CHECK_GPU(dst); CHECK_CONTIG(dst); CHECK_CONTIG(src);
-  TORCH_CHECK(!src.is_cuda() && src.is_pinned(), "h2d_stage: src must be pinned host memory");
+  const OpArgs a = on_gpu("h2d_stage", dst, "dst");
+  TORCH_CHECK(src.defined() && !src.is_cuda() && src.is_pinned() && src.is_contiguous(),
+              "h2d_stage: src must be contiguous pinned host memory");
   TORCH_CHECK(src.nbytes() == dst.nbytes(), "h2d_stage: size mismatch");
   void* dev_src = nullptr;
   TORCH_CHECK(hipHostGetDevicePointer(&dev_src, src.data_ptr(), 0) == hipSuccess,
               "h2d_stage: the pinned buffer has no device mapping");
-  const c10::DeviceGuard g(dst.device());
-  akap::launch_h2d_stage(dev_src, dst.data_ptr(), (long)dst.nbytes(), cur_stream());
+  akap::launch_h2d_stage(dev_src, a.ptr(dst, "dst", {dst.scalar_type()}), (long)dst.nbytes(),
+                         cur_stream());
 }
 
 void embedding(Tensor ids, Tensor table, Tensor out, int64_t vocab_start, int64_t vocab_end) {
-  CHECK_GPU(ids); CHECK_BF16(table); CHECK_CONTIG(table); CHECK_CONTIG(out);
-  TORCH_CHECK(ids.scalar_type() == at::kLong, "ids int64");
-  const int d = table.size(1);
-  TORCH_CHECK(d % 8 == 0, "embedding dim multiple of 8");
-  const c10::DeviceGuard g(ids.device());
-  akap::launch_embedding(ids.data_ptr<int64_t>(), table.data_ptr(), out.data_ptr(), ids.numel(),
-                         d, vocab_start, vocab_end, cur_stream());
+  const OpArgs a = on_gpu("embedding", ids, "ids");
+  TORCH_CHECK(table.dim() == 2 && table.size(1) % 8 == 0,
+              "embedding: table [V, d] with d a multiple of 8");
+  const int T = ids.numel(), d = table.size(1);
+  akap::launch_embedding(a.ptr<int64_t>(ids, "ids"), a.bf16(table, "table"),
+                         a.bf16(out, "out", (int64_t)T * d), T, d, vocab_start, vocab_end,
+                         cur_stream());
 }
 
 void embedding_prep(Tensor ids, Tensor table, Tensor ln, Tensor residual, Tensor a_out,
                     Tensor ss_out, Tensor zbuf, int64_t vocab_start, int64_t vocab_end) {
-  CHECK_GPU(ids); CHECK_BF16(table); CHECK_CONTIG(table); CHECK_BF16(ln); CHECK_CONTIG(ln);
-  CHECK_BF16(residual); CHECK_CONTIG(residual); CHECK_BF16(a_out); CHECK_CONTIG(a_out);
-  CHECK_CONTIG(ss_out); CHECK_CONTIG(zbuf);
-  TORCH_CHECK(ids.scalar_type() == at::kLong, "ids int64");
-  TORCH_CHECK(ss_out.scalar_type() == at::kFloat && zbuf.scalar_type() == at::kFloat,
-              "ss_out / zbuf fp32");
+  const OpArgs a = on_gpu("embedding_prep", ids, "ids");
+  TORCH_CHECK(table.dim() == 2, "embedding_prep: table [V, d]");
   const int T = ids.numel(), d = table.size(1);
-  TORCH_CHECK(d % 8 == 0 && ln.numel() == d, "embedding dim multiple of 8, ln of length d");
-  TORCH_CHECK(residual.numel() == (int64_t)T * d && a_out.numel() == (int64_t)T * d &&
-                  ss_out.numel() >= T,
-              "residual / a_out [T, d], ss_out >= T");
-  const c10::DeviceGuard g(ids.device());
-  akap::launch_embedding_prep(ids.data_ptr<int64_t>(), table.data_ptr(), ln.data_ptr(),
-                              residual.data_ptr(), a_out.data_ptr(), ss_out.data_ptr<float>(),
-                              zbuf.data_ptr<float>(), zbuf.numel(), T, d, vocab_start, vocab_end,
-                              cur_stream());
+  TORCH_CHECK(d % 8 == 0 && ln.numel() == d,
+              "embedding_prep: embedding dim multiple of 8, ln of length d");
+  TORCH_CHECK(residual.numel() == (int64_t)T * d && a_out.numel() == (int64_t)T * d,
+              "embedding_prep: residual / a_out [T, d]");
+  akap::launch_embedding_prep(a.ptr<int64_t>(ids, "ids"), a.bf16(table, "table"),
+                              a.bf16(ln, "ln"), a.bf16(residual, "residual"),
+                              a.bf16(a_out, "a_out"), a.ptr<float>(ss_out, "ss_out", T),
+                              a.ptr<float>(zbuf, "zbuf"), zbuf.numel(), T, d, vocab_start,
+                              vocab_end, cur_stream());
 }
 
 }  // namespace
@@ -1013,42 +933,39 @@ void car_open(int64_t h, Tensor all_handles) {
   }
 }
 
-// The IPC kernels move 16-byte vectors (bf16x8 loads / stores on the user tensors).
-static void car_check_aligned(const Tensor& a, const Tensor& b) {
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(a.data_ptr()) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(b.data_ptr()) % 16 == 0,
-              "custom collective: tensors must be 16-byte aligned");
+// The collectives' user tensors: contiguous, and 16-byte aligned (the IPC kernels move bf16x8
+// vectors on them)
+constexpr unsigned kCarVec = akap::kContig | akap::kAlign16;
+
+// every peer's buffers are mapped and the message fits one staging half
+static void car_check_ready(const CarComm* c, size_t elems) {
+  TORCH_CHECK(elems <= c->args.half_elems, "message larger than the buffer");
+  for (int p = 0; p < c->args.world; ++p)
+    TORCH_CHECK(c->args.bufs[p] != nullptr, "peer buffers not opened (call car_open)");
 }
 
 void car_all_reduce(int64_t h, Tensor inp, Tensor out, bool two_shot) {
   CarComm* c = car_get(h);
-  CHECK_GPU(inp); CHECK_BF16(inp); CHECK_CONTIG(inp); CHECK_CONTIG(out); CHECK_BF16(out);
-  TORCH_CHECK(inp.numel() == out.numel(), "size mismatch");
-  TORCH_CHECK(inp.numel() % 8 == 0, "numel % 8");
-  car_check_aligned(inp, out);
-  TORCH_CHECK((size_t)inp.numel() <= c->args.half_elems, "message larger than the buffer");
-  for (int p = 0; p < c->args.world; ++p)
-    TORCH_CHECK(c->args.bufs[p] != nullptr, "peer buffers not opened (call car_open)");
-  const c10::DeviceGuard g(inp.device());
-  akap::launch_custom_allreduce(c->args, inp.data_ptr(), out.data_ptr(), inp.numel(),
+  const OpArgs a = on_gpu("car_all_reduce", inp, "inp");
+  TORCH_CHECK(inp.numel() == out.numel(), "car_all_reduce: size mismatch");
+  TORCH_CHECK(inp.numel() % 8 == 0, "car_all_reduce: numel % 8");
+  car_check_ready(c, inp.numel());
+  akap::launch_custom_allreduce(c->args, a.bf16(inp, "inp", 0, kCarVec),
+                                a.bf16(out, "out", inp.numel(), kCarVec), inp.numel(),
                                 two_shot ? 1 : 0, cur_stream());
 }
 
-static akap::CarEpi car_epi_of(Tensor& residual, Tensor& ln, Tensor& aout, Tensor& ss,
-                               int64_t n) {
-  CHECK_BF16(residual); CHECK_CONTIG(residual); CHECK_BF16(ln); CHECK_CONTIG(ln);
-  CHECK_BF16(aout); CHECK_CONTIG(aout);
+static akap::CarEpi car_epi_of(const OpArgs& a, Tensor& residual, Tensor& ln, Tensor& aout,
+                               Tensor& ss, int64_t n) {
   const int64_t d = ln.numel();
-  TORCH_CHECK(d % 512 == 0, "car resnorm: row width must be a multiple of 512");
-  TORCH_CHECK(residual.numel() == n && aout.numel() == n && n % d == 0,
-              "car resnorm: residual / aout [M, d] like the message");
-  TORCH_CHECK(ss.scalar_type() == at::kFloat && ss.is_cuda() && ss.numel() >= n / d,
-              "car resnorm: ss fp32 [M]");
+  TORCH_CHECK(d > 0 && d % 512 == 0, a.op(), ": resnorm row width must be a multiple of 512");
+  TORCH_CHECK(residual.numel() == n && aout.numel() == n && n % d == 0, a.op(),
+              ": resnorm residual / aout [M, d] like the message");
   akap::CarEpi e{};
-  e.residual = (__bf16*)residual.data_ptr();
-  e.ln = (const __bf16*)ln.data_ptr();
-  e.aout = (__bf16*)aout.data_ptr();
-  e.ss = ss.data_ptr<float>();
+  e.residual = (__bf16*)a.bf16(residual, "residual", 0, kCarVec);
+  e.ln = (const __bf16*)a.bf16(ln, "ln", 0, kCarVec);
+  e.aout = (__bf16*)a.bf16(aout, "aout", 0, kCarVec);
+  e.ss = a.ptr<float>(ss, "ss", n / d);
   e.d = (int)d;
   return e;
 }
@@ -1059,15 +976,10 @@ static akap::CarEpi car_epi_of(Tensor& residual, Tensor& ln, Tensor& aout, Tenso
 void car_all_reduce_resnorm(int64_t h, Tensor inp, Tensor residual, Tensor ln, Tensor aout,
                             Tensor ss, bool two_shot) {
   CarComm* c = car_get(h);
-  CHECK_GPU(inp); CHECK_BF16(inp); CHECK_CONTIG(inp);
-  TORCH_CHECK((size_t)inp.numel() <= c->args.half_elems, "message larger than the buffer");
-  for (int p = 0; p < c->args.world; ++p)
-    TORCH_CHECK(c->args.bufs[p] != nullptr, "peer buffers not opened (call car_open)");
-  const akap::CarEpi e = car_epi_of(residual, ln, aout, ss, inp.numel());
-  car_check_aligned(inp, residual);
-  car_check_aligned(ln, aout);
-  const c10::DeviceGuard g(inp.device());
-  akap::launch_custom_allreduce(c->args, inp.data_ptr(), nullptr, inp.numel(),
+  const OpArgs a = on_gpu("car_all_reduce_resnorm", inp, "inp");
+  car_check_ready(c, inp.numel());
+  const akap::CarEpi e = car_epi_of(a, residual, ln, aout, ss, inp.numel());
+  akap::launch_custom_allreduce(c->args, a.bf16(inp, "inp", 0, kCarVec), nullptr, inp.numel(),
                                 two_shot ? 1 : 0, cur_stream(), &e);
 }
 
@@ -1093,24 +1005,23 @@ void car_all_reduce_multi(std::vector<int64_t> hs, std::vector<Tensor> ins,
   TORCH_CHECK(W >= 1 && W <= 8 && (int)ins.size() == W && (int)outs.size() == W, "W ranks");
   akap::CarMulti m{};
   m.warm = warm ? 1 : 0;
+  const OpArgs a = on_gpu("car_all_reduce_multi", ins[0], "ins[0]");
   const int64_t n = ins[0].numel();
   for (int r = 0; r < W; ++r) {
     CarComm* c = car_get(hs[r]);
     TORCH_CHECK(c->args.world == W && c->args.rank == r, "handles must be ranks 0..W-1");
-    CHECK_GPU(ins[r]); CHECK_BF16(ins[r]); CHECK_CONTIG(ins[r]); CHECK_CONTIG(outs[r]);
     TORCH_CHECK(ins[r].numel() == n && outs[r].numel() == n && n % 8 == 0, "sizes");
     TORCH_CHECK((size_t)n <= c->args.half_elems, "message larger than the buffer");
     m.args[r] = c->args;
-    m.in[r] = ins[r].data_ptr();
-    m.out[r] = outs[r].data_ptr();
+    m.in[r] = a.bf16(ins[r], "ins[r]");
+    m.out[r] = a.bf16(outs[r], "outs[r]");
     if (epi) {  // 4 tensors per rank: residual, ln, aout, ss
       TORCH_CHECK((int)epi->size() == 4 * W, "epi: residual, ln, aout, ss per rank");
-      m.epi[r] = car_epi_of((*epi)[4 * r], (*epi)[4 * r + 1], (*epi)[4 * r + 2],
+      m.epi[r] = car_epi_of(a, (*epi)[4 * r], (*epi)[4 * r + 1], (*epi)[4 * r + 2],
                             (*epi)[4 * r + 3], n);
       m.use_epi = 1;
     }
   }
-  const c10::DeviceGuard g(ins[0].device());
   akap::launch_custom_allreduce_multi(m, W, n, two_shot ? 1 : 0, cur_stream());
 }
 
@@ -1136,51 +1047,41 @@ Tensor car_error_word(int64_t h) {
 // Rank-major all-gather of the vocab-parallel logits shard inp [R, n] -> out [R, W*n].
 void car_all_gather(int64_t h, Tensor inp, Tensor out) {
   CarComm* c = car_get(h);
-  CHECK_GPU(inp); CHECK_BF16(inp); CHECK_CONTIG(inp); CHECK_BF16(out); CHECK_CONTIG(out);
+  const OpArgs a = on_gpu("car_all_gather", inp, "inp");
   const int64_t n = inp.size(-1);
   const int64_t rows = inp.numel() / n;
-  TORCH_CHECK(n % 8 == 0, "shard width % 8");
-  TORCH_CHECK(out.numel() == inp.numel() * c->args.world, "out [R, W*n]");
-  car_check_aligned(inp, out);
-  TORCH_CHECK((size_t)inp.numel() <= c->args.half_elems, "shard larger than the buffer");
-  for (int p = 0; p < c->args.world; ++p)
-    TORCH_CHECK(c->args.bufs[p] != nullptr, "peer buffers not opened (call car_open)");
-  const c10::DeviceGuard g(inp.device());
-  akap::launch_custom_allgather(c->args, inp.data_ptr(), out.data_ptr(), rows, (int)n,
-                                cur_stream());
+  TORCH_CHECK(n % 8 == 0, "car_all_gather: shard width % 8");
+  TORCH_CHECK(out.numel() == inp.numel() * c->args.world, "car_all_gather: out [R, W*n]");
+  car_check_ready(c, inp.numel());
+  akap::launch_custom_allgather(c->args, a.bf16(inp, "inp", 0, kCarVec),
+                                a.bf16(out, "out", 0, kCarVec), rows, (int)n, cur_stream());
 }
 
 // Equal-segment all-to-all: inp/out [world * seg] bf16, segment d of inp goes to rank d and
 // segment p of out comes from rank p.
 void car_all_to_all(int64_t h, Tensor inp, Tensor out) {
   CarComm* c = car_get(h);
-  CHECK_GPU(inp); CHECK_BF16(inp); CHECK_CONTIG(inp); CHECK_BF16(out); CHECK_CONTIG(out);
+  const OpArgs a = on_gpu("car_all_to_all", inp, "inp");
   const int64_t W = c->args.world;
   TORCH_CHECK(inp.numel() == out.numel() && inp.numel() % (W * 8) == 0,
-              "all-to-all: inp/out [world * seg] with seg % 8 == 0");
-  TORCH_CHECK((size_t)inp.numel() <= c->args.half_elems, "message larger than the buffer");
-  TORCH_CHECK(inp.data_ptr() != out.data_ptr(), "all-to-all is out of place");
-  car_check_aligned(inp, out);
-  for (int p = 0; p < c->args.world; ++p)
-    TORCH_CHECK(c->args.bufs[p] != nullptr, "peer buffers not opened (call car_open)");
-  const c10::DeviceGuard g(inp.device());
-  akap::launch_custom_alltoall(c->args, inp.data_ptr(), out.data_ptr(), inp.numel() / W,
-                               cur_stream());
+              "car_all_to_all: inp/out [world * seg] with seg % 8 == 0");
+  car_check_ready(c, inp.numel());
+  const void* src = a.bf16(inp, "inp", 0, kCarVec);
+  void* dst = a.bf16(out, "out", 0, kCarVec);
+  TORCH_CHECK(src != dst, "car_all_to_all: out of place only");
+  akap::launch_custom_alltoall(c->args, src, dst, inp.numel() / W, cur_stream());
 }
 
 // In-place broadcast of buf (any dtype, nbytes % 16 == 0) from group rank `root`.
 void car_broadcast(int64_t h, Tensor buf, int64_t root) {
   CarComm* c = car_get(h);
-  CHECK_GPU(buf); CHECK_CONTIG(buf);
+  const OpArgs a = on_gpu("car_broadcast", buf, "buf");
   const int64_t bytes = buf.numel() * buf.element_size();
-  TORCH_CHECK(bytes % 16 == 0, "broadcast bytes % 16");
-  car_check_aligned(buf, buf);
-  TORCH_CHECK((size_t)bytes <= c->args.half_elems * 2, "message larger than the buffer");
-  TORCH_CHECK(root >= 0 && root < c->args.world, "root rank");
-  for (int p = 0; p < c->args.world; ++p)
-    TORCH_CHECK(c->args.bufs[p] != nullptr, "peer buffers not opened (call car_open)");
-  const c10::DeviceGuard g(buf.device());
-  akap::launch_custom_broadcast(c->args, buf.data_ptr(), bytes, (int)root, cur_stream());
+  TORCH_CHECK(bytes % 16 == 0, "car_broadcast: bytes % 16");
+  TORCH_CHECK(root >= 0 && root < c->args.world, "car_broadcast: root rank");
+  car_check_ready(c, (size_t)(bytes + 1) / 2);
+  akap::launch_custom_broadcast(c->args, a.ptr(buf, "buf", {buf.scalar_type()}, 0, kCarVec),
+                                bytes, (int)root, cur_stream());
 }
 
 // ---------------------------------------------------------------- hipIpc of a whole tensor
@@ -1193,7 +1094,7 @@ std::vector<std::pair<int64_t, void*>>& ipc_opened() {
 }  // namespace
 
 Tensor ipc_export(Tensor t) {
-  CHECK_GPU(t);
+  TORCH_CHECK(t.defined() && t.is_cuda(), "ipc_export: t must be a GPU tensor");
   const c10::DeviceGuard g(t.device());
   hipDeviceptr_t base = nullptr;
   size_t size = 0;
