@@ -31,6 +31,9 @@ constexpr int PG_T = 256;                    // pgemm.hip: tile rows / cols
 constexpr int PG_BK = 64;                    // pgemm.hip: K tile
 constexpr int QBK = 64;                      // qgemm.hip: k per wave step
 constexpr int QGEMM_MAX_M = 256;             // rows one qgemm launch covers
+constexpr int Q4BK = 128;                    // q4gemm.hip: k per wave step (a 64-B fp4 row)
+constexpr int MXBLK = 32;                    // MXFP4: elements along K per e8m0 scale
+constexpr int Q4GEMM_MAX_M = 256;            // rows one q4gemm launch covers
 constexpr int WBK = 64;                      // wgemm.hip k-step
 constexpr int kRouterMaxE = 16;              // moe.hip fused router: experts
 
@@ -159,6 +162,26 @@ inline QGemmGeom qgemm_geometry(int M, int N, int K) {
 
 inline bool qgemm_supported(int M, int N, int K, int ldx, int ldy) {
   return M > 0 && M <= QGEMM_MAX_M && N > 0 && N % 8 == 0 && K >= QBK && K % QBK == 0 &&
+         ldx % 8 == 0 && ldy % 8 == 0;
+}
+
+// ---- q4gemm.hip ----
+// Rows and columns as qgemm_geometry, except that a 64-row tile is always 32 columns wide: at a
+// 128-deep k-step a 64-row X slot is 16 KB per wave, and two such slots per wave with a
+// 64-column weight slot do not fit the CU's 160 KB of LDS.
+inline QGemmGeom q4gemm_geometry(int M, int N, int K) {
+  QGemmGeom g = qgemm_geometry(M, N, K);
+  if (g.bm == 64) {
+    g.bn = 32;
+    g.grid = ((M + 63) / 64) * ((N + 31) / 32);
+  }
+  return g;
+}
+
+// K % 128: a wave step is 128 deep, and it makes a row of scale codes (K / 32 bytes) a whole
+// number of the 4-byte words the scale DMA moves
+inline bool q4gemm_supported(int M, int N, int K, int ldx, int ldy) {
+  return M > 0 && M <= Q4GEMM_MAX_M && N > 0 && N % 8 == 0 && K >= Q4BK && K % Q4BK == 0 &&
          ldx % 8 == 0 && ldy % 8 == 0;
 }
 

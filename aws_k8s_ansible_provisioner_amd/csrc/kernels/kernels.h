@@ -179,6 +179,22 @@ void launch_qgemm(const QGemmArgs& p, hipStream_t st);
 void launch_dequant_fp8(const void* q, const float* scale, void* out, long N, int K,
                         hipStream_t st);
 
+// ---- q4gemm.hip: MXFP4-weight (packed e2m1 codes + e8m0 block scales) decode GEMM, M <= 256 ----
+//   Y[m,n] = bf16(sum_k X[m,k] * e2m1(Wq[n,k]) * 2^(scale[n,k/32] - 127)); no workspace, no
+//   cross-workgroup state: graph-capturable and bit-reproducible
+struct Q4GemmArgs {
+  const void* X;      // bf16 [M, K] (row stride ldx)
+  const void* Wq;     // uint8 [N, K/2] contiguous: element 2j in the low nibble of byte j
+  const void* scale;  // uint8 [N, K/32] contiguous, e8m0 codes in 2..252
+  void* Y;            // bf16 [M, N] (row stride ldy)
+  int M, N, K, ldx, ldy;
+};
+// launches the tile geometry q4gemm_geometry() picks
+void launch_q4gemm(const Q4GemmArgs& p, hipStream_t st);
+// out[n, k] = bf16(e2m1(q[n, k]) * 2^(scale[n, k/32] - 127)); out bf16 [N, K], K % 32 == 0
+void launch_dequant_mxfp4(const void* q, const void* scale, void* out, long N, int K,
+                          hipStream_t st);
+
 // ---- sampling.hip ----
 struct SampleParams {
   const void* logits;  // [B, V] (row stride ld), fp32 or bf16

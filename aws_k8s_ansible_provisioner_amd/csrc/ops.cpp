@@ -503,6 +503,42 @@ void dequant_fp8(Tensor out, Tensor wq, Tensor scale) {
                            cur_stream());
 }
 
+// MXFP4-weight decode GEMM (csrc/kernels/q4gemm.hip): out[M, N] = bf16(x[M, K] @ deq(wq)^T),
+// wq = packed e2m1 codes uint8 [N, K/2], scale = e8m0 codes uint8 [N, K/32].
+void q4gemm(Tensor out, Tensor x, Tensor wq, Tensor scale) {
+  const OpArgs o = on_gpu("q4gemm", x, "x");
+  TORCH_CHECK(x.dim() == 2 && wq.dim() == 2 && out.dim() == 2 && scale.dim() == 2,
+              "q4gemm: x, wq, scale and out 2-D");
+  const int M = x.size(0), N = wq.size(0), K = 2 * wq.size(1);
+  TORCH_CHECK(x.size(1) == K && out.size(0) == M && out.size(1) == N, "q4gemm: shapes");
+  TORCH_CHECK(K % akap::MXBLK == 0 && scale.size(0) == N && scale.size(1) == K / akap::MXBLK,
+              "q4gemm: scale must be [N, K/32]");
+  TORCH_CHECK(M == 0 || akap::q4gemm_supported(M, N, K, x.stride(0), out.stride(0)),
+              "q4gemm: needs M <= 256, K >= 128, K % 128 == 0, N % 8 == 0 and 16-byte aligned "
+              "rows");
+  akap::Q4GemmArgs a{o.bf16(x, "x", 0, kLastContig | kAlign16),
+                     o.ptr<uint8_t>(wq, "wq", (int64_t)N * (K / 2), kContig | kAlign16),
+                     o.ptr<uint8_t>(scale, "scale", (int64_t)N * (K / akap::MXBLK),
+                                    kContig | kAlign16),
+                     o.bf16(out, "out", 0, kLastContig | kAlign16),
+                     M, N, K, (int)x.stride(0), (int)out.stride(0)};
+  akap::launch_q4gemm(a, cur_stream());
+}
+
+// out[N, K] bf16 = e2m1(wq) * 2^(scale - 127), exact
+void dequant_mxfp4(Tensor out, Tensor wq, Tensor scale) {
+  const OpArgs o = on_gpu("dequant_mxfp4", wq, "wq");
+  TORCH_CHECK(wq.dim() == 2 && out.dim() == 2 && scale.dim() == 2, "dequant_mxfp4: dims");
+  const int64_t N = wq.size(0), K = 2 * wq.size(1);
+  TORCH_CHECK(K % akap::MXBLK == 0, "dequant_mxfp4: K % 32 == 0");
+  TORCH_CHECK(out.size(0) == N && out.size(1) == K && scale.size(0) == N &&
+                  scale.size(1) == K / akap::MXBLK, "dequant_mxfp4: shapes");
+  const unsigned vec = kContig | kAlign16;
+  akap::launch_dequant_mxfp4(o.ptr<uint8_t>(wq, "wq", N * (K / 2), vec),
+                             o.ptr<uint8_t>(scale, "scale", N * (K / akap::MXBLK)),
+                             o.bf16(out, "out", N * K, vec), N, (int)K, cur_stream());
+}
+
 // Narrow-output decode GEMM with the K split inside the workgroup (csrc/kernels/kgemm.hip):
 // out = x @ w^T (rows scaled by rsqrt(ss_in / K + eps) when ss_in is given), epi 0 store,
 // 1 residual/next-norm (out = residual in/out, aout = bf16(out * ln_out), ss_out += row sums).
@@ -1211,6 +1247,8 @@ TORCH_LIBRARY(akap, m) {
   m.def("wgemm(Tensor(a!) out, Tensor x, Tensor w) -> ()");
   m.def("qgemm(Tensor(a!) out, Tensor x, Tensor wq, Tensor scale) -> ()");
   m.def("dequant_fp8(Tensor(a!) out, Tensor wq, Tensor scale) -> ()");
+  m.def("q4gemm(Tensor(a!) out, Tensor x, Tensor wq, Tensor scale) -> ()");
+  m.def("dequant_mxfp4(Tensor(a!) out, Tensor wq, Tensor scale) -> ()");
   m.def("pgemm(Tensor(a!) out, Tensor x, Tensor w, int epi=0, Tensor? offs=None) -> ()");
   m.def("kgemm(Tensor(a!) out, Tensor x, Tensor w, int bm, int epi, float eps, Tensor? ss_in, "
         "Tensor(b!)? ss_out, Tensor(c!)? aout, Tensor? ln_out) -> ()");
@@ -1292,6 +1330,8 @@ TORCH_LIBRARY_IMPL(akap, CUDA, m) {
   m.impl("wgemm", &wgemm);
   m.impl("qgemm", &qgemm);
   m.impl("dequant_fp8", &dequant_fp8);
+  m.impl("q4gemm", &q4gemm);
+  m.impl("dequant_mxfp4", &dequant_mxfp4);
   m.impl("pgemm", &pgemm);
   m.impl("kgemm", &kgemm);
   m.impl("moe_topk_softmax", &moe_topk_softmax);

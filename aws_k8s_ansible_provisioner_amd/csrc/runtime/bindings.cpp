@@ -79,6 +79,13 @@ static void bind_contract(py::module_ m) {
     const QGemmGeom g = qgemm_geometry(M, N, K);
     return py::make_tuple(g.bm, g.bn, g.grid);
   });
+  m.attr("Q4GEMM_MAX_M") = Q4GEMM_MAX_M;
+  m.attr("Q4GEMM_BK") = Q4BK;
+  m.def("q4gemm_supported", &q4gemm_supported);
+  m.def("q4gemm_geometry", [](int M, int N, int K) {
+    const QGemmGeom g = q4gemm_geometry(M, N, K);
+    return py::make_tuple(g.bm, g.bn, g.grid);
+  });
   m.def("moe_router_topk_supported", &moe_router_topk_supported);
   // -> (supported, family 0 ring | 1 lds | 2 pgemm_sk, combines in launch, ws floats, ticket ints)
   m.def("dgemm_contract", [](int M, int N, int K, int pro, int epi, int splitk, int pf, int bn,

@@ -41,16 +41,18 @@ class EngineConfig:
     # samples) before waiting for step N, so host bookkeeping and the graph launch overlap
     # the GPU (single-rank engines with hipGraphs; AKAP_ASYNC_DECODE=0 disables)
     async_decode: bool = True
-    # weight quantization: "fp8" = per-channel e4m3fn weights, bf16 activations (dense layer
-    # projections only); "none" = bf16.  None takes AKAP_QUANTIZATION from the environment
+    # weight quantization: "fp8" = per-channel e4m3fn weights, "mxfp4" = e2m1 weights with one
+    # e8m0 scale per 32 elements along K; bf16 activations (dense layer projections only);
+    # "none" = bf16.  None takes AKAP_QUANTIZATION from the environment
     # (unset: bf16); an explicit value, "none" included, wins over the variable
     quantization: Optional[str] = None
 
     def __post_init__(self) -> None:
         if self.quantization is None:
             self.quantization = os.environ.get("AKAP_QUANTIZATION") or None
-        if self.quantization not in (None, "none", "fp8"):
-            raise ValueError(f"quantization must be none or fp8, got {self.quantization!r}")
+        if self.quantization not in (None, "none", "fp8", "mxfp4"):
+            raise ValueError(f"quantization must be none, fp8 or mxfp4, "
+                             f"got {self.quantization!r}")
         # the K cache stores each 32-token chunk in MFMA-fragment order (ops/reference.py)
         if self.block_size <= 0 or self.block_size % 32:
             raise ValueError(f"block_size must be a multiple of 32, got {self.block_size}")

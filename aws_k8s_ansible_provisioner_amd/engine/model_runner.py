@@ -65,14 +65,18 @@ class ModelRunner:
             from .weights import load_safetensors_dir
 
             self.model.load_state_dict(load_safetensors_dir(ecfg.weights_path))
-        if ecfg.quantization == "fp8":
+        if ecfg.quantization in ("fp8", "mxfp4"):
             # after the weights are in place and before the KV cache is sized: the freed bf16
             # projections go back to the allocator so _derive_num_blocks sees that HBM
-            self.model.quantize_fp8()
+            if ecfg.quantization == "fp8":
+                self.model.quantize_fp8()
+            else:
+                self.model.quantize_mxfp4()
             bf16_gib = self.model.weight_bytes(as_bf16=True) / 2**30
             if self.is_gpu:
                 torch.cuda.empty_cache()
-            self.log(f"[runner] fp8 weights: {self.model.weight_bytes() / 2**30:.2f} GiB/rank "
+            self.log(f"[runner] {ecfg.quantization} weights: "
+                     f"{self.model.weight_bytes() / 2**30:.2f} GiB/rank "
                      f"(bf16 {bf16_gib:.2f} GiB; embedding, LM head and norms stay bf16)")
         self.log(f"[runner] model {mcfg.name} ready in {time.time() - t0:.1f}s "
                  f"({self.model.weight_bytes() / 2**30:.2f} GiB weights/rank)")

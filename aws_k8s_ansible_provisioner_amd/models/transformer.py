@@ -22,7 +22,8 @@ import torch.nn.functional as F
 
 from .. import ops
 from ..ops import reference as ref
-from ..ops.quant import Fp8Weight, quantize_fp8, reserve_scratch
+from ..ops.quant import (Fp8Weight, Mxfp4Weight, QuantWeight, quantize_fp8, quantize_mxfp4,
+                         reserve_scratch)
 from ..parallel import comm
 from ..parallel.state import ParallelState, get_state
 from .config import ModelConfig
@@ -82,20 +83,37 @@ def _shard_cols(w, rank: int, size: int):
 
 
 PROJECTIONS = ("w_qkv", "w_o", "w_gate_up", "w_down")
-QUANTIZATIONS = (None, "fp8")
+QUANTIZATIONS = (None, "fp8", "mxfp4")
+_QUANTIZERS = {"fp8": quantize_fp8, "mxfp4": quantize_mxfp4}
 _FP8_BLOCK = 128  # block-scaled checkpoints: one weight_scale_inv per 128 x 128 block
 
 
-def _checkpoint_proj(sd: dict, key: str, quantized: bool):
-    """The projection `key`.weight of a checkpoint: a plain tensor, or an Fp8Weight for a
+def _scale_kind(t: torch.Tensor) -> str:
+    """Which quantization a checkpoint's `weight_scale` tensor belongs to: e8m0 codes (uint8)
+    are MXFP4 block scales, anything else an FP8 scale."""
+    return "mxfp4" if t.dtype in (torch.uint8, getattr(torch, "float8_e8m0fnu", None)) else "fp8"
+
+
+def _checkpoint_proj(sd: dict, key: str, quantization: Optional[str]):
+    """The projection `key`.weight of a checkpoint: a plain tensor, an Mxfp4Weight for packed
+    e2m1 codes (uint8 [N, K/2]) with e8m0 `weight_scale` codes (uint8 [N, K/32]), or an Fp8Weight
+    for a
     pre-quantized float8_e4m3fn weight with a per-channel ([N, 1] / [N]) or per-tensor (scalar,
     expanded) `weight_scale`.  A block-scaled weight (`weight_scale_inv`, 128 x 128 blocks) is
     dequantized to fp32 here and re-quantized per channel by the caller.  `input_scale`
     (activation scales of W8A8 checkpoints) is not used: activations stay bf16."""
     w = sd[key + ".weight"]
+    if w.dtype in (torch.uint8, getattr(torch, "float4_e2m1fn_x2", None)):
+        if quantization != "mxfp4":
+            raise ValueError(f"{key}.weight holds packed 4-bit codes: this is an MXFP4 "
+                             f"checkpoint, load it with --quantization mxfp4")
+        if key + ".weight_scale" not in sd:
+            raise ValueError(f"{key}.weight is MXFP4 but the checkpoint has no "
+                             f"{key}.weight_scale")
+        return Mxfp4Weight(w, sd[key + ".weight_scale"])  # refuses e8m0 codes outside 2..252
     if w.dtype != torch.float8_e4m3fn:
         return w
-    if not quantized:
+    if quantization != "fp8":
         raise ValueError(f"{key}.weight is float8_e4m3fn: this is an FP8 checkpoint, load it "
                          f"with --quantization fp8")
     N, K = w.shape
@@ -119,7 +137,10 @@ def _fuse_rows(parts: list):
     (codes and per-channel scales are concatenated), fp32 otherwise."""
     if all(isinstance(p, Fp8Weight) for p in parts):
         return Fp8Weight(torch.cat([p.q for p in parts], 0), torch.cat([p.scale for p in parts], 0))
-    if any(isinstance(p, Fp8Weight) or p.dtype == torch.float32 for p in parts):
+    if all(isinstance(p, Mxfp4Weight) for p in parts):
+        return Mxfp4Weight(torch.cat([p.q for p in parts], 0),
+                           torch.cat([p.scale for p in parts], 0), check=False)
+    if any(isinstance(p, QuantWeight) or p.dtype == torch.float32 for p in parts):
         return torch.cat([p.float() for p in parts], 0)
     return torch.cat(parts, 0)
 
@@ -162,14 +183,14 @@ class DecoderLM:
         if quantization == "none":
             quantization = None
         if quantization not in QUANTIZATIONS:
-            raise ValueError(f"unknown quantization {quantization!r} (none | fp8)")
-        if quantization == "fp8" and cfg.is_moe:
-            raise ValueError(f"{cfg.name}: fp8 weight quantization covers dense models only "
+            raise ValueError(f"unknown quantization {quantization!r} (none | fp8 | mxfp4)")
+        if quantization is not None and cfg.is_moe:
+            raise ValueError(f"{cfg.name}: {quantization} weight quantization covers dense models only "
                              f"(MoE experts are not quantized)")
-        # "fp8": load_state_dict accepts FP8 checkpoints and quantizes plain ones; a model
-        # built from random weights is quantized by quantize_fp8()
+        # "fp8" / "mxfp4": load_state_dict accepts checkpoints of that kind and quantizes plain
+        # ones; a model built from random weights is quantized by quantize_fp8 / quantize_mxfp4
         self.quantization = quantization
-        self.quantized = False  # some layer projection is an Fp8Weight
+        self.quantized = False  # some layer projection is a QuantWeight
         self.cfg = cfg
         self.init_std = init_std
         self.device = torch.device(device)
@@ -279,7 +300,8 @@ class DecoderLM:
 
     def weight_bytes(self, as_bf16: bool = False) -> int:
         """bf16 tensors at 2 bytes per element; a quantized projection [N, K] counts
-        N * K + 4 * N (codes + fp32 scales), or what it would take in bf16 with as_bf16."""
+        N * K + 4 * N (fp8 codes + fp32 scales) or N * K / 2 + N * K / 32 (MXFP4 codes + block
+        scales), or what it would take in bf16 with as_bf16."""
         n = self.embed.numel() + self.final_norm.numel()
         q = 0
         if self.lm_head is not self.embed:
@@ -287,7 +309,7 @@ class DecoderLM:
         for lw in self.layers:
             for t in (lw.ln1, lw.ln2, lw.w_qkv, lw.w_o, lw.q_norm, lw.k_norm, lw.w_gate_up,
                       lw.w_down):
-                if isinstance(t, Fp8Weight):
+                if isinstance(t, QuantWeight):
                     q += 2 * t.numel() if as_bf16 else t.nbytes
                 elif t is not None:
                     n += t.numel()
@@ -301,19 +323,28 @@ class DecoderLM:
         at a time, dropping each bf16 tensor as it goes.  Embedding, LM head and norms stay
         bf16, as in published FP8 checkpoints.  Also reserves the dequantization scratch the
         prefill path uses (ops.quant), sized to the largest quantized weight."""
+        self._quantize("fp8")
+
+    @torch.no_grad()
+    def quantize_mxfp4(self) -> None:
+        """The same for MXFP4: e2m1 codes with one e8m0 scale per 32 elements along K
+        (Mxfp4Weight), after the bf16 weights are resident."""
+        self._quantize("mxfp4")
+
+    def _quantize(self, kind: str) -> None:
         if any(lw.moe is not None for lw in self.layers):
-            raise ValueError(f"{self.cfg.name}: fp8 weight quantization covers dense models "
+            raise ValueError(f"{self.cfg.name}: {kind} weight quantization covers dense models "
                              f"only (MoE experts are not quantized)")
         largest = 0
         for lw in self.layers:
             for name in PROJECTIONS:
                 w = getattr(lw, name)
-                if not isinstance(w, Fp8Weight):
+                if not isinstance(w, QuantWeight):
                     setattr(lw, name, None)
-                    w = quantize_fp8(w)
+                    w = _QUANTIZERS[kind](w)
                     setattr(lw, name, w)
                 largest = max(largest, w.numel())
-        self.quantization = "fp8"
+        self.quantization = kind
         self.quantized = True
         reserve_scratch(largest, self.device)
 
@@ -332,8 +363,12 @@ class DecoderLM:
         q, kv = self.hq * D, self.hkv * D
 
         def put(key: str, w, a: int = 0, b: Optional[int] = None) -> None:
-            # rows [a, b) of a projection; quantized: float8_e4m3fn codes + [N, 1] fp32 scales
-            if isinstance(w, Fp8Weight):
+            # rows [a, b) of a projection; quantized: float8_e4m3fn codes + [N, 1] fp32 scales,
+            # or packed e2m1 codes uint8 [N, K/2] + e8m0 codes uint8 [N, K/32]
+            if isinstance(w, Mxfp4Weight):
+                sd[key + ".weight"] = w.q[a:b].clone()
+                sd[key + ".weight_scale"] = w.scale[a:b].clone()
+            elif isinstance(w, Fp8Weight):
                 sd[key + ".weight"] = w.q[a:b].clone().view(torch.float8_e4m3fn)
                 sd[key + ".weight_scale"] = w.scale[a:b].clone().reshape(-1, 1)
             else:
@@ -361,18 +396,18 @@ class DecoderLM:
 
     def _set_proj(self, lw: LayerWeights, name: str, src) -> None:
         """Store one (fused, sharded) projection.  bf16 model: copy into the existing tensor.
-        fp8 model: a pre-quantized source is kept bit for bit (no bf16 detour); any other
-        source is quantized per channel from its own precision."""
+        Quantized model: a pre-quantized source is kept bit for bit (no bf16 detour); any other
+        source is quantized from its own precision."""
         cur = getattr(lw, name)
         if tuple(src.shape) != tuple(cur.shape):
             raise ValueError(f"{name}: checkpoint shape {tuple(src.shape)} != model "
                              f"{tuple(cur.shape)}")
-        if self.quantization != "fp8":
+        if self.quantization is None:
             cur.copy_(src.to(cur.dtype))
             return
         setattr(lw, name, None)  # drop the old weight before the new one is resident
-        if not isinstance(src, Fp8Weight):
-            src = quantize_fp8(src.to(self.device))
+        if not isinstance(src, QuantWeight):
+            src = _QUANTIZERS[self.quantization](src.to(self.device))
         setattr(lw, name, src.to(self.device))
         self.quantized = True
         reserve_scratch(src.numel(), self.device)
@@ -380,15 +415,16 @@ class DecoderLM:
     def load_state_dict(self, sd: dict) -> None:
         """Load HF-named tensors (safetensors from the model PVC) into the fused layout.
         With quantization "fp8" the projections may be plain (quantized here), pre-quantized
-        float8_e4m3fn + `weight_scale`, or block-scaled (`weight_scale_inv`)."""
+        float8_e4m3fn + `weight_scale`, or block-scaled (`weight_scale_inv`); with "mxfp4",
+        plain or pre-quantized uint8 [N, K/2] + uint8 `weight_scale` [N, K/32]."""
         cfg, tp, r = self.cfg, self.ps.tp_size, self.ps.tp_rank
-        fp8 = self.quantization == "fp8"
-        if not fp8:
-            for k in sd:
-                if k.endswith((".weight_scale", ".weight_scale_inv")):
-                    raise ValueError(f"checkpoint key {k}: this is an FP8 checkpoint, load it "
-                                     f"with --quantization fp8")
-        proj = lambda key: _checkpoint_proj(sd, key, fp8)  # noqa: E731
+        for k in sd:
+            if k.endswith((".weight_scale", ".weight_scale_inv")):
+                kind = _scale_kind(sd[k])
+                if kind != self.quantization:
+                    raise ValueError(f"checkpoint key {k}: this is an {kind.upper()} checkpoint, "
+                                     f"load it with --quantization {kind}")
+        proj = lambda key: _checkpoint_proj(sd, key, self.quantization)  # noqa: E731
         cp = lambda dst, src: dst.copy_(src.to(dst.dtype))  # noqa: E731
         emb = sd["model.embed_tokens.weight"]
         n = self.vocab_end - self.vocab_start

@@ -20,7 +20,8 @@ import torch
 from .._runtime_loader import contract as _contract
 from . import reference as ref
 from .gemm_variant import Variant
-from .quant import Fp8Weight, linear_fp8, quantize_fp8  # noqa: F401
+from .quant import (Fp8Weight, Mxfp4Weight, QuantWeight, linear_fp8,  # noqa: F401
+                    linear_quant, quantize_fp8, quantize_mxfp4)
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _LIB = os.path.join(_PKG, "_C.so")
@@ -311,9 +312,9 @@ def _use_pgemm(x: torch.Tensor, w: torch.Tensor, silu: bool = False) -> bool:
 def linear_silu(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     """silu(x @ gate.T) * (x @ up.T) for the [gate; up] weight w [2F, K]: one pgemm launch
     with the SwiGLU epilogue for prefill-sized M (no [M, 2F] intermediate round trip through
-    HBM), else linear + silu_and_mul.  An Fp8Weight takes linear + silu_and_mul."""
-    if isinstance(w, Fp8Weight):
-        return silu_and_mul(linear_fp8(x, w))
+    HBM), else linear + silu_and_mul.  A quantized weight takes linear + silu_and_mul."""
+    if isinstance(w, QuantWeight):
+        return silu_and_mul(linear_quant(x, w))
     if _use_pgemm(x, w, silu=True):
         load_native(required=True)
         return pgemm(x, w, silu=True)
@@ -323,10 +324,11 @@ def linear_silu(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
 def linear(x: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """y = x @ w.T.  Decode-sized M on the GPU -> the hand-written MFMA GEMM (small tiles +
     split-K to fill 256 CUs); large M (prefill) -> hipBLASLt via torch, or the hand-written
-    256 x 256 pgemm where it measured faster (AKAP_PREFILL_GEMM).  w may be an Fp8Weight
-    (ops/quant.py): M <= 256 -> the fp8-weight qgemm, else dequantize + this bf16 path."""
-    if isinstance(w, Fp8Weight):
-        return linear_fp8(x, w, out=out)
+    256 x 256 pgemm where it measured faster (AKAP_PREFILL_GEMM).  w may be an Fp8Weight or
+    an Mxfp4Weight (ops/quant.py): M <= 256 -> the weight-streaming qgemm / q4gemm, else
+    dequantize + this bf16 path."""
+    if isinstance(w, QuantWeight):
+        return linear_quant(x, w, out=out)
     M = x.shape[0]
     split = None
     if _use_pgemm(x, w):

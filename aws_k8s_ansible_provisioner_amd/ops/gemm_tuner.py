@@ -275,7 +275,7 @@ def tune_model(model, Ms: Sequence[int], log=print) -> dict:
     for lw in model.layers:
         for name in ("w_qkv", "w_o", "w_gate_up", "w_down"):
             w = getattr(lw, name, None)
-            # a quantized projection (ops.quant.Fp8Weight) runs qgemm, which has no candidates
+            # a quantized projection (ops.quant.QuantWeight) runs qgemm / q4gemm: no candidates
             if isinstance(w, torch.Tensor):
                 groups.setdefault((name, tuple(w.shape)), []).append(w)
     summary = {}

@@ -1,4 +1,4 @@
-"""FP8 (OCP e4m3fn) weight-only quantization, W8A16.
+"""Weight-only quantization: FP8 (OCP e4m3fn, W8A16) and MXFP4 (OCP e2m1 + e8m0, W4A16).
 
 A quantized projection weight is ``Fp8Weight(q, scale)``: ``q`` uint8 [N, K] holding e4m3fn
 codes (never the NaN codes 0x7F / 0xFF), ``scale`` fp32 [N], one value per output channel.
@@ -8,6 +8,17 @@ codes (never the NaN codes 0x7F / 0xFF), ``scale`` fp32 [N], one value per outpu
 accumulated in fp32.  Activations stay bf16: every e4m3 value is exact in bf16, so the GPU
 kernel (csrc/kernels/qgemm.hip) streams 1-byte weights, widens them in registers and runs the
 bf16 MFMA; the scale multiplies the fp32 accumulators.
+
+``Mxfp4Weight(q, scale)``: ``q`` uint8 [N, K/2] holding two e2m1 codes per byte (element 2j in
+the low nibble of byte j, element 2j+1 in the high nibble: torch.float4_e2m1fn_x2's packing),
+``scale`` uint8 [N, K/32], one e8m0 code s (value 2^(s-127), 2 <= s <= 252) per 32 elements
+along K.
+
+    Y[m, n] = bf16(sum_k float(X[m, k]) * e2m1(q[n, k]) * 2^(scale[n, k/32] - 127))
+
+accumulated in fp32.  An e2m1 value times such a power of two is exact in bf16, so the GPU
+kernel (csrc/kernels/q4gemm.hip) streams half-byte weights and widens them, block scale
+included, in registers.
 """
 from __future__ import annotations
 
@@ -100,6 +111,125 @@ def quantize_fp8(w: torch.Tensor) -> Fp8Weight:
     return Fp8Weight(q.view(torch.uint8), scale)
 
 
+# ------------------------------------------------------------------ MXFP4
+MX_BLOCK = 32                      # elements along K that share one e8m0 scale
+MX_SCALE_MIN, MX_SCALE_MAX = 2, 252  # accepted e8m0 codes: 0.5 * 2^e and 6 * 2^e normal in bf16
+_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+class Mxfp4Weight:
+    """MXFP4 weight [N, K]: packed e2m1 codes uint8 [N, K/2] and e8m0 block scales uint8
+    [N, K/32]; stands where a bf16 weight tensor did."""
+
+    __slots__ = ("q", "scale")
+
+    def __init__(self, q: torch.Tensor, scale: torch.Tensor, check: bool = True):
+        fp4 = getattr(torch, "float4_e2m1fn_x2", None)
+        if fp4 is not None and q.dtype == fp4:
+            q = q.view(torch.uint8)
+        e8m0 = getattr(torch, "float8_e8m0fnu", None)
+        if e8m0 is not None and scale.dtype == e8m0:
+            scale = scale.view(torch.uint8)
+        if q.dtype != torch.uint8 or q.dim() != 2:
+            raise ValueError("Mxfp4Weight: q must be a 2-D uint8 tensor [N, K/2]")
+        if q.shape[1] % (MX_BLOCK // 2):
+            raise ValueError(f"Mxfp4Weight: K = {2 * q.shape[1]} must be a multiple of {MX_BLOCK}")
+        if (scale.dtype != torch.uint8 or scale.dim() != 2
+                or tuple(scale.shape) != (q.shape[0], q.shape[1] // (MX_BLOCK // 2))):
+            raise ValueError("Mxfp4Weight: scale must be uint8 [N, K/32] (e8m0 codes)")
+        # check=False: slices and copies of a weight that was checked when it was built
+        bad = (scale < MX_SCALE_MIN) | (scale > MX_SCALE_MAX)
+        if check and scale.numel() and bool(bad.any()):
+            raise ValueError(f"Mxfp4Weight: e8m0 scale codes must lie in [{MX_SCALE_MIN}, "
+                             f"{MX_SCALE_MAX}] (255 is NaN; outside, a dequantized value is not "
+                             f"a normal bf16 number)")
+        self.q = q.contiguous()
+        self.scale = scale.contiguous()
+
+    @property
+    def shape(self) -> torch.Size:
+        return torch.Size((self.q.shape[0], 2 * self.q.shape[1]))
+
+    @property
+    def device(self) -> torch.device:
+        return self.q.device
+
+    @property
+    def is_cuda(self) -> bool:
+        return self.q.is_cuda
+
+    @property
+    def dtype(self) -> torch.dtype:
+        return getattr(torch, "float4_e2m1fn_x2", torch.uint8)
+
+    def dim(self) -> int:
+        return 2
+
+    def numel(self) -> int:
+        return 2 * self.q.numel()
+
+    @property
+    def nbytes(self) -> int:
+        """N * K / 2 code bytes + N * K / 32 scale bytes."""
+        return self.q.numel() + self.scale.numel()
+
+    def float(self) -> torch.Tensor:
+        """The dequantized fp32 matrix e2m1(q) * 2^(scale - 127) (exact)."""
+        lut = torch.tensor(_E2M1 + tuple(-v for v in _E2M1), dtype=torch.float32,
+                           device=self.device)
+        q = self.q.long()
+        v = torch.stack((lut[q & 15], lut[q >> 4]), dim=-1).reshape(self.shape)
+        s = torch.ldexp(torch.ones((), device=self.device), self.scale.to(torch.int32) - 127)
+        return v * s.repeat_interleave(MX_BLOCK, dim=1)
+
+    def __getitem__(self, idx) -> "Mxfp4Weight":
+        """Row / column slices (tensor-parallel sharding): w[a:b] slices codes and scales by
+        rows, w[:, a:b] by columns, where a and b must be multiples of 32 (whole scale blocks)."""
+        rows, cols = idx if isinstance(idx, tuple) else (idx, slice(None))
+        if not (isinstance(rows, slice) and isinstance(cols, slice)):
+            raise TypeError("Mxfp4Weight supports slices only")
+        a, b, step = cols.indices(self.shape[1])
+        if step != 1 or a % MX_BLOCK or b % MX_BLOCK:
+            raise ValueError(f"Mxfp4Weight: column slice [{a}:{b}] must start and end on "
+                             f"multiples of {MX_BLOCK}")
+        return Mxfp4Weight(self.q[rows, a // 2:b // 2],
+                           self.scale[rows, a // MX_BLOCK:b // MX_BLOCK], check=False)
+
+    def to(self, device) -> "Mxfp4Weight":
+        return Mxfp4Weight(self.q.to(device), self.scale.to(device), check=False)
+
+    def __repr__(self) -> str:
+        return f"Mxfp4Weight(shape={tuple(self.shape)}, device={self.device})"
+
+
+# what ops.linear / linear_silu, the loader and the byte accounting test a weight against
+QuantWeight = (Fp8Weight, Mxfp4Weight)
+
+
+@torch.no_grad()
+def quantize_mxfp4(w: torch.Tensor) -> Mxfp4Weight:
+    """The OCP MX rule per block of 32 along K: e = floor(log2(amax)) - 2 (scale code e + 127,
+    clamped to 2..252; 127 for an all-zero block), code = RNE(w / 2^e) onto the e2m1 grid
+    {0, .5, 1, 1.5, 2, 3, 4, 6}, saturated at +-6."""
+    if w.dim() != 2 or w.shape[1] % MX_BLOCK:
+        raise ValueError(f"quantize_mxfp4: 2-D weight with K a multiple of {MX_BLOCK}")
+    N, K = w.shape
+    w32 = w.float().reshape(N, K // MX_BLOCK, MX_BLOCK)
+    amax = w32.abs().amax(dim=2)
+    ex = torch.frexp(amax)[1] - 1  # floor(log2(amax)), exact (amax = m * 2^(ex + 1), m in [.5, 1))
+    code = torch.where(amax > 0, ex - 2 + 127, torch.full_like(ex, 127))
+    code = code.clamp_(MX_SCALE_MIN, MX_SCALE_MAX)
+    a = torch.ldexp(w32.abs(), (127 - code)[:, :, None])  # |w| / 2^e, exact
+    # RNE onto the grid: steps of 0.5 below 2, of 1 below 4, of 2 above (torch.round is
+    # round-half-to-even, and the even neighbour is the even e2m1 mantissa at every tie)
+    r = torch.where(a < 2, torch.round(a * 2) / 2,
+                    torch.where(a < 4, torch.round(a), torch.round(a / 2) * 2)).clamp_(max=6.0)
+    grid = torch.tensor(_E2M1, dtype=torch.float32, device=w.device)
+    c = torch.bucketize(r, grid)
+    c = torch.where((w32 < 0) & (c > 0), c + 8, c).to(torch.uint8).reshape(N, K)
+    return Mxfp4Weight(c[:, 0::2] | (c[:, 1::2] << 4), code.to(torch.uint8), check=False)
+
+
 # ------------------------------------------------------------------ dequantization scratch
 # One bf16 buffer per device, as large as the largest quantized weight: the prefill / mixed
 # step path dequantizes a weight into it and runs the bf16 GEMM on it.  The NEXT call reuses
@@ -178,3 +308,63 @@ def linear_fp8(x: torch.Tensor, w: Fp8Weight, out: Optional[torch.Tensor] = None
         raise ValueError(f"fp8 weight {tuple(w.shape)}: K must be a multiple of 16")
     # prefill and mixed steps: dequantize into the shared scratch, then the bf16 GEMM
     return linear(x, _dequant_to_scratch(w), out=out)
+
+
+# ------------------------------------------------------------------ MXFP4 on the GPU
+def dequant_mxfp4(w: Mxfp4Weight, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """bf16(e2m1(q) * 2^(scale - 127)) as a new (or given) bf16 tensor; GPU: the HIP kernel."""
+    if out is None:
+        out = torch.empty(w.shape, dtype=torch.bfloat16, device=w.device)
+    if w.is_cuda:
+        from . import load_native
+
+        load_native(required=True)
+        torch.ops.akap.dequant_mxfp4(out, w.q, w.scale)
+    else:
+        out.copy_(w.float().to(torch.bfloat16))
+    return out
+
+
+def q4gemm_supported(x: torch.Tensor, w: Mxfp4Weight, out: Optional[torch.Tensor] = None) -> bool:
+    """Whether torch.ops.akap.q4gemm takes the launch: the kernel's shape predicate and the
+    tensor properties ops.cpp checks (out=None: a fresh dense [M, N] output)."""
+    N, K = w.shape
+    return (x.dim() == 2 and x.dtype == torch.bfloat16 and x.stride(-1) == 1
+            and x.data_ptr() % 16 == 0
+            and (out is None or (out.dim() == 2 and out.stride(-1) == 1
+                                 and out.data_ptr() % 16 == 0))
+            and _contract().q4gemm_supported(x.shape[0], N, K, x.stride(0),
+                                             N if out is None else out.stride(0)))
+
+
+def linear_mxfp4(x: torch.Tensor, w: Mxfp4Weight,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y = x @ w.T for an Mxfp4Weight (the contract at the top of this file)."""
+    if not x.is_cuda:
+        y = (x.float() @ w.float().t()).to(x.dtype)
+        if out is not None:
+            out.copy_(y)
+            return out
+        return y
+    from . import linear, load_native
+
+    load_native(required=True)
+    if x.shape[0] == 0:
+        return out if out is not None else x.new_empty(0, w.shape[0])
+    if q4gemm_supported(x, w, out):
+        if out is None:
+            out = torch.empty(x.shape[0], w.shape[0], dtype=x.dtype, device=x.device)
+        torch.ops.akap.q4gemm(out, x, w.q, w.scale)
+        return out
+    # prefill and mixed steps: dequantize into the shared scratch, then the bf16 GEMM
+    reserve_scratch(w.numel(), w.device)
+    wd = _scratch[w.device][: w.numel()].view(w.shape)
+    torch.ops.akap.dequant_mxfp4(wd, w.q, w.scale)
+    return linear(x, wd, out=out)
+
+
+def linear_quant(x: torch.Tensor, w, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y = x @ w.T for any QuantWeight."""
+    if isinstance(w, Mxfp4Weight):
+        return linear_mxfp4(x, w, out=out)
+    return linear_fp8(x, w, out=out)

@@ -635,9 +635,11 @@ def make_parser() -> argparse.ArgumentParser:
     ap.add_argument("--kv-cache-dtype", default="auto", choices=["auto", "fp8", "fp8_e4m3"],
                     help="fp8: OCP e4m3 KV cache (half the bytes; decode attention streams "
                          "half as much)")
-    ap.add_argument("--quantization", default=None, choices=["none", "fp8"],
+    ap.add_argument("--quantization", default=None, choices=["none", "fp8", "mxfp4"],
                     help="fp8: per-channel e4m3 weights for the dense layer projections (bf16 "
                          "activations; loads FP8 checkpoints, quantizes bf16 ones at start-up). "
+                         "mxfp4: e2m1 weights with one e8m0 scale per 32 elements along K, same "
+                         "scope (loads uint8 weight + weight_scale checkpoints). "
                          "Default: AKAP_QUANTIZATION, else none")
     ap.add_argument("--otlp-traces-endpoint", default=None,
                     help="OTLP/HTTP collector (e.g. http://otel-collector:4318); also read "

@@ -1,13 +1,13 @@
-"""Microbench of the FP8-weight decode GEMM (csrc/kernels/qgemm.hip) against the bf16 path it
-replaces: ops.linear's tuned choice for the shape (gemm_tuner.tune: hipBLASLt or the fastest
-hand-written bf16 variant), for the four dense projections of Qwen3-0.6B and of Llama-3-8B at
+"""Microbench of the FP8-weight decode GEMM (csrc/kernels/qgemm.hip) and the MXFP4-weight one
+(csrc/kernels/q4gemm.hip) against the bf16 path they replace: ops.linear's tuned choice for the
+shape (gemm_tuner.tune: hipBLASLt or the fastest hand-written bf16 variant), for the four dense projections of Qwen3-0.6B and of Llama-3-8B at
 M in {1, 16, 64, 256}.
 
-Both paths are timed on COLD weights: the launches rotate over copies of the weight worth
+All three paths are timed on COLD weights: the launches rotate over copies of the weight worth
 >= 768 MB (3x the 256 MB MALL, gemm_tuner._rot), inside one captured graph.
 
     python tools/qgemm_bench.py [--json qgemm.json] [--models qwen3-0.6b,llama-3-8b]
-Prints one line per (shape, M): us and effective weight GB/s (weight bytes / time) of both."""
+Prints one line per (shape, M): us and effective weight GB/s (weight bytes / time) of each."""
 from __future__ import annotations
 
 import argparse
@@ -22,7 +22,7 @@ import torch  # noqa: E402
 from aws_k8s_ansible_provisioner_amd import ops  # noqa: E402
 from aws_k8s_ansible_provisioner_amd.models.config import get_config  # noqa: E402
 from aws_k8s_ansible_provisioner_amd.ops import gemm_tuner  # noqa: E402
-from aws_k8s_ansible_provisioner_amd.ops.quant import quantize_fp8  # noqa: E402
+from aws_k8s_ansible_provisioner_amd.ops.quant import quantize_fp8, quantize_mxfp4  # noqa: E402
 
 MS = (1, 16, 64, 256)
 COLD_BYTES = 768 << 20
@@ -53,6 +53,8 @@ def main() -> int:
             wb = [src.to(torch.bfloat16).clone() for _ in range(copies(2 * N * K))]
             q = quantize_fp8(src)
             wq = [(q.q.clone(), q.scale.clone()) for _ in range(copies(N * K))]
+            q4 = quantize_mxfp4(src)
+            w4 = [(q4.q.clone(), q4.scale.clone()) for _ in range(copies(q4.nbytes))]
             del src
             for M in MS:
                 x = torch.randn(M, K, device=dev, dtype=torch.bfloat16)
@@ -62,16 +64,21 @@ def main() -> int:
                 nq = len(wq)
                 t_q = gemm_tuner._timed(
                     lambda i: torch.ops.akap.qgemm(y, x, wq[i % nq][0], wq[i % nq][1]), nq)
+                n4 = len(w4)
+                t_4 = gemm_tuner._timed(
+                    lambda i: torch.ops.akap.q4gemm(y, x, w4[i % n4][0], w4[i % n4][1]), n4)
                 r = {"model": model, "proj": name, "M": M, "N": N, "K": K,
                      "bf16": gemm_tuner._label(choice), "bf16_us": round(t_b, 2),
                      "fp8_us": round(t_q, 2),
                      "bf16_gbs": round(2 * N * K / t_b / 1e3, 1),
                      "fp8_gbs": round((N * K + 4 * N) / t_q / 1e3, 1),
-                     "speedup": round(t_b / t_q, 3)}
+                     "speedup": round(t_b / t_q, 3),
+                     "mxfp4_us": round(t_4, 2), "mxfp4_gbs": round(q4.nbytes / t_4 / 1e3, 1),
+                     "fp8_over_mxfp4": round(t_q / t_4, 3), "bf16_over_mxfp4": round(t_b / t_4, 3)}
                 rows.append(r)
                 print(json.dumps(r), flush=True)
                 del x, y
-            del wb, wq
+            del wb, wq, w4
             torch.cuda.empty_cache()
     if a.json:
         os.makedirs(os.path.dirname(a.json) or ".", exist_ok=True)
