@@ -436,3 +436,223 @@ def exact_gemm_expected(yi: torch.Tensor, unit: float, epi: int = 0,
     g, u = y[:, :F].double(), y[:, F:].double()
     sg = bf16_rne(g / (1.0 + torch.exp(-g)))
     return ExactExpected(bf16_rne(sg.double() * u))
+
+
+# ----------------------------------------------------------------------------- attention probes
+# Inputs for which paged attention's output is known without an attention reference
+# (tests/test_attention_probes_*): a NEEDLE query is beta times one cached key, so that key
+# scores ~beta * |k|^2 / sqrt(D) nats above keys that score beta * N(0, 1); the softmax is
+# one-hot far below fp32 resolution and the output is the target's V row itself.  One wrong
+# key, one rolled V group or one leaked stale slot then misses by order 1, not by 1 / kv_len.
+#
+# The stale-slot contract the poison encodes: cache slots at positions >= kv_len of a
+# sequence's last block (the rest of its last 8-token V group included) and the blocks that
+# unused block-table entries name hold FINITE values and are never attended.  The kernels
+# multiply P = 0 into whatever V holds there, so a NaN or Inf would propagate by design; the
+# engine's caches start zero-initialised.  Every block id stays in range: an out-of-range id
+# would be an out-of-bounds read, not a probe.
+NEEDLE_BETA = 4.0
+POISON_K_GAIN = 8.0
+POISON_V = 1e30          # bf16: 1e30; e4m3: clamps to 448
+NEEDLE_ABS_FLOOR = 1e-6  # e4m3 V holds exact zeros; there the other keys' residue shows
+
+
+def write_tokens(k_cache, v_cache, blocks, K, V) -> None:
+    """Whole blocks at once: K, V [len(blocks) * BS, Hkv, D] in token order -> the paged
+    layouts (the inverse of gather_kv over `blocks`)."""
+    NB, H, BS, D = k_cache.shape
+    blocks = blocks.long()
+    nb = blocks.numel()
+    assert K.shape == (nb * BS, H, D) and V.shape == K.shape
+    arr = torch.empty(nb, BS // 32, 32, H, D, dtype=k_cache.dtype)
+    arr[:, :, K_CHUNK_POS] = to_cache(K, k_cache).reshape(nb, BS // 32, 32, H, D)
+    arr = arr.reshape(nb, BS // 32, 2, 16, H, D // 32, 32).permute(0, 4, 1, 2, 5, 3, 6)
+    k_blocks_view(k_cache)[blocks] = arr
+    # tokens [nb, BS/8, 8, H, D] -> [nb, H, BS/8, D, 8]
+    v_cache[blocks] = to_cache(V, v_cache).reshape(nb, BS // 8, 8, H, D).permute(0, 3, 1, 4, 2)
+
+
+def poison_direction(Hkv: int, D: int, seed: int) -> torch.Tensor:
+    """[Hkv, D] bf16: the direction every poisoned K slot holds POISON_K_GAIN times."""
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(Hkv, D, generator=g).bfloat16()
+
+
+def poison_stale(k_cache, v_cache, block_tables, seq_lens, poison_block: int,
+                 pdir: torch.Tensor, keep_group=()) -> None:
+    """Poison, in place, what no sequence may attend (the contract above): every slot at a
+    position >= kv_len of each sequence's last block gets K = POISON_K_GAIN * pdir and
+    V = POISON_V, block `poison_block` (which no sequence owns) gets them in every slot, and
+    the block-table entries past each sequence's last block point at it.  Sequences must not
+    share blocks with longer ones."""
+    BS = k_cache.shape[2]
+    pk = pdir.float() * POISON_K_GAIN
+    pv = torch.full_like(pk, POISON_V)
+    for o in range(BS):
+        write_k(k_cache, poison_block, o, pk)
+        v_cache[poison_block, :, o // 8, :, o % 8] = to_cache(pv, v_cache)
+    for s in range(seq_lens.numel()):
+        L = int(seq_lens[s])
+        nb = (L + BS - 1) // BS
+        block_tables[s, nb:] = poison_block
+        if L % BS == 0:
+            continue
+        b = int(block_tables[s, nb - 1])
+        assert b != poison_block
+        for o in range(L % BS, BS):
+            write_k(k_cache, b, o, pk)
+            v_cache[b, :, o // 8, :, o % 8] = to_cache(pv, v_cache)
+
+
+def needle_q(K: torch.Tensor, targets: torch.Tensor, G: int, beta: float = NEEDLE_BETA,
+             unit: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """q [T, Hq, D] = bf16(beta * K[targets[t, h], h // G]) for K [n, Hkv, D] in token order.
+    unit [T, Hq] bool: those rows are scaled to length beta * sqrt(D) instead, whatever the
+    key's own length (the forbidden needles, whose key may be poison)."""
+    T, Hq = targets.shape
+    kvh = (torch.arange(Hq) // G).expand(T, Hq)
+    k = K.float()[targets.long(), kvh]                      # [T, Hq, D]
+    q = beta * k
+    if unit is not None:
+        qn = beta * math.sqrt(k.shape[-1]) * k / k.norm(dim=-1, keepdim=True).clamp_min(1e-20)
+        q = torch.where(unit[..., None], qn, q)
+    return q.to(torch.bfloat16)
+
+
+def needle_expect(V: torch.Tensor, targets: torch.Tensor, G: int) -> torch.Tensor:
+    """[T, Hq, D] bf16: V[targets[t, h], h // G] for V [n, Hkv, D] in token order."""
+    T, Hq = targets.shape
+    kvh = (torch.arange(Hq) // G).expand(T, Hq)
+    return V[targets.long(), kvh].to(torch.bfloat16)
+
+
+def unrope(x: torch.Tensor, positions: torch.Tensor, cos_sin: torch.Tensor) -> torch.Tensor:
+    """The inverse of apply_rope (the rotation is orthogonal): x [T, H, D] float."""
+    half = cos_sin.shape[1] // 2
+    inv = torch.cat([cos_sin[:, :half], -cos_sin[:, half:]], dim=-1)
+    return apply_rope(x, positions, inv)
+
+
+def needle_mismatch(out: torch.Tensor, expect: torch.Tensor):
+    """Needle comparator: -> (bad [..] bool per element, largest bf16 ulp distance among the
+    elements the absolute floor does not excuse).  An element passes within one bf16 ulp of
+    the expected V entry or within NEEDLE_ABS_FLOOR of it."""
+    out, expect = out.cpu(), expect.cpu()
+    finite = torch.isfinite(out.float())
+    ulp = bf16_ulp_distance(out, expect)
+    near = (out.float() - expect.float()).abs() <= NEEDLE_ABS_FLOOR
+    bad = ~finite | ((ulp > 1) & ~near)
+    seen = torch.where(near | ~finite, torch.zeros_like(ulp), ulp)
+    return bad, int(seen.max()) if seen.numel() else 0
+
+
+def close_mismatch(out: torch.Tensor, expect: torch.Tensor, tol: float):
+    """-> (bad per element, worst err / limit) for |out - expect| <= tol + tol * |expect|."""
+    o, e = out.float().cpu(), expect.float().cpu()
+    lim = tol + tol * e.abs()
+    err = (o - e).abs()
+    err = torch.where(torch.isfinite(o), err, torch.full_like(err, float("inf")))
+    return err > lim, float((err / lim).max()) if err.numel() else 0.0
+
+
+# Score patterns: key j's log2-domain score is a chosen function of j, constant or linear
+# over `tile` keys (the prefill kernel's 64-key tile, the decode kernel's 32-key chunk), so the
+# running maximum of a flash-style loop moves exactly where the pattern says.
+SCORE_PATTERNS = ("rise6", "rise10", "step7.9", "step8.1", "fall10", "saw12", "spikes", "creep2",
+                  "peak10")
+
+
+def score_pattern(name: str, n: int, tile: int) -> torch.Tensor:
+    """float64 [n]: the log2-domain score of key j.
+      rise6 / rise10   linear, +6 / +10 per tile (crosses an 8-unit threshold every second
+                       tile / every tile)
+      step7.9/step8.1  constant per tile, +7.9 / +8.1 per tile (either side of the threshold)
+      fall10           linear, -10 per tile from 10 * tiles (the first tile holds the maximum)
+      saw12            constant per tile: 0, 12, 24, 0, 12, 24, ...
+      spikes           0 everywhere but +900 on one key of the second tile and +1000 on one key
+                       of the second-to-last tile
+      creep2           constant per tile: 0, then 7.5 + 2 per tile (creeps past the threshold)
+      peak10           +10 per tile up to the tile at a third of the context, then -10 per tile
+                       (the maximum sits in an early split-KV partition)"""
+    j = torch.arange(n, dtype=torch.float64)
+    t = torch.div(j, tile, rounding_mode="floor")
+    nt = (n + tile - 1) // tile
+    if name == "rise6":
+        return 6.0 * j / tile
+    if name == "rise10":
+        return 10.0 * j / tile
+    if name == "step7.9":
+        return 7.9 * t
+    if name == "step8.1":
+        return 8.1 * t
+    if name == "fall10":
+        return 10.0 * nt - 10.0 * j / tile
+    if name == "saw12":
+        return 12.0 * (t % 3)
+    if name == "spikes":
+        s = torch.zeros(n, dtype=torch.float64)
+        if n > tile + 5:
+            s[tile + 5] = 900.0
+        if nt >= 4:
+            s[(nt - 2) * tile + tile // 2] = 1000.0
+        return s
+    if name == "creep2":
+        return torch.where(t == 0, torch.zeros_like(t), 7.5 + 2.0 * (t - 1))
+    if name == "peak10":
+        top = nt // 3
+        return 10.0 * (top - (t - top).abs())
+    raise ValueError(name)
+
+
+def pattern_kq(scores: torch.Tensor, Hkv: int, rows: int, Hq: int, scale: float, seed: int,
+               beta: float = NEEDLE_BETA, D: int = 128):
+    """K [n, Hkv, D] (float) and q [rows, Hq, D] bf16 whose log2-domain scores
+    q . k * scale * log2(e) follow `scores` [n]: K = c_j u + noise, q = beta u + noise, both
+    noises orthogonal to the sign vector u (|u|^2 = 2), so the noise only decorrelates the
+    bf16 roundings and adds a few hundredths of a unit of score."""
+    g = torch.Generator().manual_seed(seed)
+    n = scores.numel()
+    u = (torch.randint(0, 2, (Hkv, D), generator=g).double() * 2 - 1) * 0.125
+    c = scores.double() / (beta * 2.0 * scale * math.log2(math.e))
+
+    def perp(x, uu):  # remove the component along u
+        return x - (x * uu).sum(-1, keepdim=True) / 2.0 * uu
+    kn = perp(torch.randn(n, Hkv, D, generator=g, dtype=torch.float64) * 0.25, u[None])
+    K = c[:, None, None] * u[None] + kn
+    uq = u.repeat_interleave(Hq // Hkv, dim=0)                # [Hq, D]
+    qn = perp(torch.randn(rows, Hq, D, generator=g, dtype=torch.float64) * 0.02, uq[None])
+    q = (beta * uq[None] + qn).to(torch.bfloat16)
+    return K.float(), q
+
+
+def fa_tile_model(s2: torch.Tensor, V: torch.Tensor, limit: int, T: float = 8.0,
+                  tile: int = 64, rescale_o: bool = True):
+    """A from-scratch model of one row of a flash-style tile loop with a deferred running
+    maximum -- the specification the prefill kernel's loop is read against, not a port of it.
+    s2 [n] float64 log2-domain scores, V [n, D]; keys 0..limit are visible.  Per `tile` keys:
+    the running max m moves to the tile's max only when that exceeds m + T (T = 0: the exact
+    max); P = bf16(2^(s - m)) feeds o, its fp32 value feeds l; o and l are fp32 and are
+    rescaled by 2^(m_old - m_new) when m moves.  -> (o / l as float64 [D], number of moves
+    of m after the first tile).  rescale_o=False leaves o unscaled (the bug the rising
+    patterns must expose)."""
+    m = float("-inf")
+    l = torch.zeros((), dtype=torch.float32)
+    o = torch.zeros(V.shape[1], dtype=torch.float32)
+    moves = 0
+    Vb = V.to(torch.bfloat16).float()
+    for k0 in range(0, limit + 1, tile):
+        k1 = min(k0 + tile, limit + 1)
+        s = s2[k0:k1]
+        mc = max(m, float(s.max()))
+        m_new = mc if mc > m + T else m
+        if m_new != m:
+            alpha = torch.tensor(2.0 ** (m - m_new), dtype=torch.float32)
+            l = l * alpha
+            if rescale_o:
+                o = o * alpha
+            moves += k0 > 0
+            m = m_new
+        p = torch.exp2((s - m).float())
+        l = l + p.sum()
+        o = o + p.to(torch.bfloat16).float() @ Vb[k0:k1]
+    return (o.double() / l.double()), int(moves)
