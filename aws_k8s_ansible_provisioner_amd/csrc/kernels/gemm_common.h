@@ -1,5 +1,5 @@
 // Device helpers shared by the GEMM kernels (gemm / dgemm / gdgemm / kgemm / wgemm / qgemm /
-// pgemm / moe_dgemm): LDS swizzle and LDS-DMA staging, counted waits, the epilogue arithmetic
+// pgemm / moe_dgemm / moe_qgemm): LDS swizzle and LDS-DMA staging, counted waits, the epilogue arithmetic
 // whose rounding order is a contract with the CPU reference, and the split-K ticket step.
 #pragma once
 
@@ -34,6 +34,15 @@ __device__ __forceinline__ void wait_vm() {
 }
 
 __device__ __forceinline__ float silu_bf(float g) { return bf2f(f2bf(g / (1.f + __expf(-g)))); }
+
+// ---- per-channel scaled (FP8-weight) epilogues: moe_qgemm.hip ---------------------------------
+// The rounding order, a contract with the CPU reference (ops/quant.py): the scale of the weight
+// row multiplies the fp32 accumulator BEFORE the first rounding.
+//   store   y    = bf16(scale[e, n] * acc)
+//   SILU    g    = bf16(s_gate * acc_gate),  u = bf16(s_up * acc_up),  y = bf16(silu_bf(g) * u)
+//           with s_gate / s_up the scales of the weight rows the gate/up interleave read
+//   split   P[z] = scale[e, n] * acc_z   (fp32; moe_combine_split sums the slices)
+// qgemm.hip's store epilogue follows the same rule with scale[n].
 
 // ---- EPI_RESNORM arithmetic -----------------------------------------------------------------
 // The fused residual / next-norm rounding order, a contract with the CPU reference and

@@ -193,6 +193,18 @@ inline bool moe_dgemm_supported(int N, int K, int pf, int silu, int splitk) {
   return silu ? N % 32 == 0 : N % 8 == 0;
 }
 
+// ---- moe_qgemm.hip: the FP8-expert form; a ring step is MQBK deep, and a slice whose depth is
+// an odd multiple of MBK ends in a half step, so pf = 1 takes every (N, K, silu, splitk) that
+// moe_dgemm_supported takes for some pf ----
+constexpr int MQBK = 128;
+inline bool moe_qgemm_supported(int N, int K, int pf, int silu, int splitk) {
+  if (pf != 1 && pf != 2 && pf != 4) return false;
+  if (N <= 0 || K <= 0 || splitk < 1 || K % splitk || (K / splitk) % MBK) return false;
+  if (((K / splitk + MQBK - 1) / MQBK) % pf) return false;
+  if (silu && splitk > 1) return false;
+  return silu ? N % 32 == 0 : N % 8 == 0;
+}
+
 inline bool moe_router_topk_supported(int E, int d) {
   return E >= 1 && E <= kRouterMaxE && d % 8 == 0;
 }

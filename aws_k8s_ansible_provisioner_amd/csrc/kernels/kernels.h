@@ -236,6 +236,16 @@ void launch_moe_dgemm(const void* A, const void* W, void* Y, const int32_t* sort
 void launch_moe_combine_split(const float* P, const float* wts, const int32_t* inv, void* out,
                               int T, int topk, int d, int S, int rows, hipStream_t s);
 
+// ---- moe_qgemm.hip ----
+// The same grouped GEMM over FP8 expert weights: Wq uint8 [E, N, K] (OCP e4m3fn codes), scale
+// fp32 [E, N]; the scale multiplies the fp32 accumulator before the first rounding
+// (gemm_common.h).  No workspace, no cross-workgroup state.
+void launch_moe_qgemm(const void* A, const void* Wq, const float* scale, void* Y,
+                      const int32_t* sorted_ids, const int32_t* tile_expert, int max_tiles,
+                      int n_flat, int topk, int N, int K, int lda, int ldy, int gather, int silu,
+                      int pf, int bm, int splitk, float* partials, bool nt_weights,
+                      hipStream_t s);
+
 // ---- moe.hip ----
 void launch_moe_topk_softmax(const void* logits, int ld, int E, int K, float* topk_w,
                              int32_t* topk_ids, int T, int renormalize, hipStream_t s);

@@ -86,6 +86,8 @@ static void bind_contract(py::module_ m) {
     const QGemmGeom g = q4gemm_geometry(M, N, K);
     return py::make_tuple(g.bm, g.bn, g.grid);
   });
+  m.def("moe_dgemm_supported", &moe_dgemm_supported);
+  m.def("moe_qgemm_supported", &moe_qgemm_supported);
   m.def("moe_router_topk_supported", &moe_router_topk_supported);
   // -> (supported, family 0 ring | 1 lds | 2 pgemm_sk, combines in launch, ws floats, ticket ints)
   m.def("dgemm_contract", [](int M, int N, int K, int pro, int epi, int splitk, int pf, int bn,

@@ -46,8 +46,18 @@ class EngineConfig:
     # "none" = bf16.  None takes AKAP_QUANTIZATION from the environment
     # (unset: bf16); an explicit value, "none" included, wins over the variable
     quantization: Optional[str] = None
+    # MoE expert weights only: "fp8" = per-(expert, channel) e4m3fn expert weights (attention
+    # projections, router, embedding, LM head and norms stay bf16; `quantization` must be none
+    # on an MoE model); "none" = bf16.  None takes AKAP_EXPERT_QUANTIZATION from the environment
+    # (unset: bf16); an explicit value, "none" included, wins over the variable
+    expert_quantization: Optional[str] = None
 
     def __post_init__(self) -> None:
+        if self.expert_quantization is None:
+            self.expert_quantization = os.environ.get("AKAP_EXPERT_QUANTIZATION") or None
+        if self.expert_quantization not in (None, "none", "fp8"):
+            raise ValueError(f"expert_quantization must be none or fp8, "
+                             f"got {self.expert_quantization!r}")
         if self.quantization is None:
             self.quantization = os.environ.get("AKAP_QUANTIZATION") or None
         if self.quantization not in (None, "none", "fp8", "mxfp4"):

@@ -60,7 +60,8 @@ class ModelRunner:
         self.model = DecoderLM(mcfg, self.device, seed=ecfg.seed, pstate=self.ps,
                                max_model_len=ecfg.max_model_len, init_std=ecfg.init_std,
                                full_then_shard=ecfg.shard_init == "full",
-                               quantization=ecfg.quantization)
+                               quantization=ecfg.quantization,
+                               expert_quantization=ecfg.expert_quantization)
         if ecfg.load_format == "safetensors" and ecfg.weights_path:
             from .weights import load_safetensors_dir
 
@@ -78,6 +79,16 @@ class ModelRunner:
             self.log(f"[runner] {ecfg.quantization} weights: "
                      f"{self.model.weight_bytes() / 2**30:.2f} GiB/rank "
                      f"(bf16 {bf16_gib:.2f} GiB; embedding, LM head and norms stay bf16)")
+        if ecfg.expert_quantization == "fp8":
+            # same place as above: the freed bf16 experts count for the KV cache
+            self.model.quantize_experts_fp8()
+            bf16_gib = self.model.weight_bytes(as_bf16=True) / 2**30
+            if self.is_gpu:
+                torch.cuda.empty_cache()
+            self.log(f"[runner] fp8 expert weights: "
+                     f"{self.model.weight_bytes() / 2**30:.2f} GiB/rank "
+                     f"(bf16 {bf16_gib:.2f} GiB; attention projections, router, embedding, "
+                     f"LM head and norms stay bf16)")
         self.log(f"[runner] model {mcfg.name} ready in {time.time() - t0:.1f}s "
                  f"({self.model.weight_bytes() / 2**30:.2f} GiB weights/rank)")
         self.bs = ecfg.block_size

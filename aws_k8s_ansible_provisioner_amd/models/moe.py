@@ -39,6 +39,8 @@ import torch
 import torch.nn.functional as F
 
 from .. import ops
+from ..ops.quant import (Fp8Experts, Fp8Weight, dequant_fp8_experts, quantize_fp8,
+                         quantize_fp8_experts)
 from ..parallel import comm
 from ..parallel.state import ParallelState
 
@@ -130,6 +132,31 @@ class MoEBlock:
     def numel(self) -> int:
         return self.router.numel() + self.w13.numel() + self.w2.numel()
 
+    @property
+    def quantized(self) -> bool:
+        return isinstance(self.w13, Fp8Experts)
+
+    @torch.no_grad()
+    def quantize_fp8(self) -> None:
+        """Replace this rank's expert weights (its local experts in ep mode, its F shard in tp
+        mode) by Fp8Experts, one tensor at a time: each bf16 tensor is dropped before the next
+        quantized one is made.  The router stays bf16."""
+        for name in ("w13", "w2"):
+            w = getattr(self, name)
+            if not isinstance(w, Fp8Experts):
+                setattr(self, name, None)
+                q = quantize_fp8_experts(w)
+                del w
+                setattr(self, name, q)
+
+    def weight_bytes(self, as_bf16: bool = False) -> int:
+        """The router and plain experts at 2 bytes per element; Fp8Experts at their nbytes
+        (codes + fp32 scales), or at 2 bytes per element with as_bf16."""
+        n = 2 * self.router.numel()
+        for w in (self.w13, self.w2):
+            n += w.nbytes if isinstance(w, Fp8Experts) and not as_bf16 else 2 * w.numel()
+        return n
+
     def _hf_names(self, prefix: str, e: int) -> tuple:
         """HF checkpoint names: (router, gate, up, down) of expert e -- Mixtral's
         block_sparse_moe.{gate, experts.e.w1/w3/w2} or Qwen3-MoE's mlp.{gate,
@@ -142,9 +169,48 @@ class MoEBlock:
         return (prefix + "block_sparse_moe.gate.weight", p + "w1.weight", p + "w3.weight",
                 p + "w2.weight")
 
-    def load_state_dict(self, sd: dict, prefix: str) -> None:
+    def _load_fp8(self, prefix: str, proj) -> None:
+        """Expert weights of a checkpoint as Fp8Experts.  proj(key) is the projection `key`.weight:
+        an Fp8Weight for a pre-quantized tensor with a per-channel or per-tensor `weight_scale`
+        (kept bit for bit; gate and up are concatenated along N with their scales), else a
+        plain or (block-scaled source) fp32 tensor, quantized per channel here."""
+        r = self.ps.tp_rank
+        d, fl = self.cfg.hidden_size, self.f_local
+        fs = slice(None) if self.mode == "ep" else slice(r * fl, (r + 1) * fl)
+
+        def q8(parts: list) -> Fp8Weight:
+            if all(isinstance(p, Fp8Weight) for p in parts):
+                return Fp8Weight(torch.cat([p.q for p in parts], 0),
+                                 torch.cat([p.scale for p in parts], 0))
+            return quantize_fp8(torch.cat([p.float() for p in parts], 0).to(self.device))
+
+        def fill(name: str, N: int, K: int, expert) -> None:
+            setattr(self, name, None)  # drop the old tensor before the new one is resident
+            q = torch.empty(self.e_local, N, K, dtype=torch.uint8, device=self.device)
+            s = torch.empty(self.e_local, N, dtype=torch.float32, device=self.device)
+            for j in range(self.e_local):
+                w = expert(self.e0 + j)
+                if tuple(w.shape) != (N, K):
+                    raise ValueError(f"{prefix}expert {self.e0 + j} {name}: checkpoint shape "
+                                     f"{tuple(w.shape)} != model {(N, K)}")
+                q[j].copy_(w.q)
+                s[j].copy_(w.scale)
+            setattr(self, name, Fp8Experts(q, s))
+
+        key = lambda n: n[:-len(".weight")]  # noqa: E731
+        names = lambda e: self._hf_names(prefix, e)  # noqa: E731
+        fill("w13", 2 * fl, d, lambda e: q8([proj(key(names(e)[1]))[fs],
+                                             proj(key(names(e)[2]))[fs]]))
+        fill("w2", d, fl, lambda e: q8([proj(key(names(e)[3]))[:, fs]]))
+
+    def load_state_dict(self, sd: dict, prefix: str, fp8_proj=None) -> None:
+        """fp8_proj: with expert quantization on, the checkpoint accessor (DecoderLM) through
+        which the experts are loaded as Fp8Experts."""
         r, tp = self.ps.tp_rank, self.ps.tp_size
         self.router.copy_(sd[self._hf_names(prefix, 0)[0]])
+        if fp8_proj is not None:
+            self._load_fp8(prefix, fp8_proj)
+            return
         for j in range(self.e_local):
             e = self.e0 + j
             _, n1, n3, n2 = self._hf_names(prefix, e)
@@ -163,6 +229,12 @@ class MoEBlock:
         sd = {self._hf_names(prefix, 0)[0]: self.router.clone()}
         for e in range(self.E):
             _, n1, n3, n2 = self._hf_names(prefix, e)
+            if self.quantized:
+                # float8_e4m3fn codes + [N, 1] fp32 weight_scale, as DecoderLM.hf_state_dict
+                for n, w in ((n1, self.w13[e][:Fn]), (n3, self.w13[e][Fn:]), (n2, self.w2[e])):
+                    sd[n] = w.q.clone().view(torch.float8_e4m3fn)
+                    sd[n[:-len(".weight")] + ".weight_scale"] = w.scale.clone().reshape(-1, 1)
+                continue
             sd[n1] = self.w13[e, :Fn].clone()
             sd[n3] = self.w13[e, Fn:].clone()
             sd[n2] = self.w2[e].clone()
@@ -264,6 +336,16 @@ class MoEBlock:
         replaces (profiles/r3_moe_prefill.log).  Outputs come back in row order (a permutation
         store: deterministic, no float atomics), or with sorted_out as (expert-sorted rows,
         order) for a caller that gathers them itself."""
+        if self.quantized and not x.is_cuda:
+            # CPU reference path of FP8 experts: the exact contract (ref.fused_moe dequantizes
+            # exactly), every row one (token, expert) pair of weight 1
+            xs = x if src is None else x[src]
+            ones = torch.ones(xs.shape[0], 1, dtype=torch.float32, device=x.device)
+            y = ops.fused_moe(xs, self.w13, self.w2, ones, e.reshape(-1, 1).to(torch.int32))
+            if sorted_out:
+                order = torch.sort(e.reshape(-1).long(), stable=True)[1]
+                return y[order], order
+            return y
         e = e.reshape(-1).long()
         el = self.e_local
         # empty fixed-dispatch slots (id -1) sort last into a dummy group past the final offset:
@@ -275,15 +357,21 @@ class MoEBlock:
         offs = torch.searchsorted(ks, torch.arange(el, device=ks.device, dtype=ks.dtype),
                                   right=True).to(torch.int32)
         xs = x[order if src is None else src[order]]
-        if ops.use_pgemm(xs, self.w13.shape[1], silu=True, grouped=True):
+        # FP8 experts: each tensor is dequantized (dequant_fp8 kernel, bit-exact) into the shared
+        # scratch right before the grouped GEMM that reads it; the w2 view reuses the bytes of
+        # the w13 view in stream order, like the dense layers' scratch reuse
+        w13 = dequant_fp8_experts(self.w13) if self.quantized else self.w13
+        if ops.use_pgemm(xs, w13.shape[1], silu=True, grouped=True):
             # hand-written grouped GEMM with SwiGLU in its epilogue (csrc/kernels/pgemm.hip)
-            a = ops.pgemm(xs, self.w13, silu=True, offs=offs)
+            a = ops.pgemm(xs, w13, silu=True, offs=offs)
         else:
-            a = ops.silu_and_mul(torch._grouped_mm(xs, self.w13.transpose(1, 2), offs=offs))
-        if ops.use_pgemm(a, self.w2.shape[1], grouped=True):
-            y = ops.pgemm(a, self.w2, offs=offs)
+            a = ops.silu_and_mul(torch._grouped_mm(xs, w13.transpose(1, 2), offs=offs))
+        del w13
+        w2 = dequant_fp8_experts(self.w2) if self.quantized else self.w2
+        if ops.use_pgemm(a, w2.shape[1], grouped=True):
+            y = ops.pgemm(a, w2, offs=offs)
         else:
-            y = torch._grouped_mm(a, self.w2.transpose(1, 2), offs=offs)
+            y = torch._grouped_mm(a, w2.transpose(1, 2), offs=offs)
         if sorted_out:
             return y, order
         out = torch.empty_like(y)

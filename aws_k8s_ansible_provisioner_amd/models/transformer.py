@@ -84,6 +84,7 @@ def _shard_cols(w, rank: int, size: int):
 
 PROJECTIONS = ("w_qkv", "w_o", "w_gate_up", "w_down")
 QUANTIZATIONS = (None, "fp8", "mxfp4")
+EXPERT_QUANTIZATIONS = (None, "fp8")  # MoE expert weights only (Fp8Experts)
 _QUANTIZERS = {"fp8": quantize_fp8, "mxfp4": quantize_mxfp4}
 _FP8_BLOCK = 128  # block-scaled checkpoints: one weight_scale_inv per 128 x 128 block
 
@@ -179,14 +180,28 @@ class DecoderLM:
                  dtype: torch.dtype = torch.bfloat16, seed: int = 0,
                  pstate: Optional[ParallelState] = None, max_model_len: int = 4096,
                  full_then_shard: bool = False, init_std: float = 0.02,
-                 quantization: Optional[str] = None):
+                 quantization: Optional[str] = None,
+                 expert_quantization: Optional[str] = None):
         if quantization == "none":
             quantization = None
         if quantization not in QUANTIZATIONS:
             raise ValueError(f"unknown quantization {quantization!r} (none | fp8 | mxfp4)")
         if quantization is not None and cfg.is_moe:
             raise ValueError(f"{cfg.name}: {quantization} weight quantization covers dense models only "
-                             f"(MoE experts are not quantized)")
+                             f"(MoE experts are not quantized by --quantization; see "
+                             f"--expert-quantization)")
+        if expert_quantization == "none":
+            expert_quantization = None
+        if expert_quantization not in EXPERT_QUANTIZATIONS:
+            raise ValueError(f"unknown expert quantization {expert_quantization!r} (none | fp8)")
+        if expert_quantization is not None and not cfg.is_moe:
+            raise ValueError(f"{cfg.name}: expert quantization set on a dense model (no experts); "
+                             f"use --quantization")
+        # "fp8": load_state_dict loads the experts as Fp8Experts (pre-quantized kept bit for bit,
+        # plain ones quantized); a model built from random weights is quantized by
+        # quantize_experts_fp8.  Everything but the experts stays bf16.
+        self.expert_quantization = expert_quantization
+        self.experts_quantized = False  # the MoE blocks hold Fp8Experts
         # "fp8" / "mxfp4": load_state_dict accepts checkpoints of that kind and quantizes plain
         # ones; a model built from random weights is quantized by quantize_fp8 / quantize_mxfp4
         self.quantization = quantization
@@ -313,9 +328,27 @@ class DecoderLM:
                     q += 2 * t.numel() if as_bf16 else t.nbytes
                 elif t is not None:
                     n += t.numel()
-            if lw.moe is not None:
-                n += lw.moe.numel()
+            if lw.moe is not None:  # quantized experts [E, N, K]: E * N * K + 4 * E * N
+                q += lw.moe.weight_bytes(as_bf16)
         return n * 2 + q
+
+    @torch.no_grad()
+    def quantize_experts_fp8(self) -> None:
+        """Replace every MoE layer's expert weights by per-(expert, channel) e4m3fn Fp8Experts,
+        one tensor at a time.  Router, attention projections, embedding, LM head and norms stay
+        bf16 (`quantized` stays false: the dense-layer logic is untouched).  Also reserves the
+        dequantization scratch the prefill path uses, sized to the largest expert tensor
+        (E_local * 2F * d elements)."""
+        if not self.cfg.is_moe:
+            raise ValueError(f"{self.cfg.name}: a dense model has no experts to quantize")
+        largest = 0
+        for lw in self.layers:
+            if lw.moe is not None:
+                lw.moe.quantize_fp8()
+                largest = max(largest, lw.moe.w13.numel(), lw.moe.w2.numel())
+        self.expert_quantization = "fp8"
+        self.experts_quantized = True
+        reserve_scratch(largest, self.device)
 
     @torch.no_grad()
     def quantize_fp8(self) -> None:
@@ -334,7 +367,8 @@ class DecoderLM:
     def _quantize(self, kind: str) -> None:
         if any(lw.moe is not None for lw in self.layers):
             raise ValueError(f"{self.cfg.name}: {kind} weight quantization covers dense models "
-                             f"only (MoE experts are not quantized)")
+                             f"only (MoE experts are not quantized by it; see "
+                             f"quantize_experts_fp8 / --expert-quantization)")
         largest = 0
         for lw in self.layers:
             for name in PROJECTIONS:
@@ -418,13 +452,35 @@ class DecoderLM:
         float8_e4m3fn + `weight_scale`, or block-scaled (`weight_scale_inv`); with "mxfp4",
         plain or pre-quantized uint8 [N, K/2] + uint8 `weight_scale` [N, K/32]."""
         cfg, tp, r = self.cfg, self.ps.tp_size, self.ps.tp_rank
+        eq = self.expert_quantization
         for k in sd:
             if k.endswith((".weight_scale", ".weight_scale_inv")):
                 kind = _scale_kind(sd[k])
-                if kind != self.quantization:
+                if eq is not None and ".experts." in k:
+                    # expert tensors are judged against the expert knob
+                    if kind != eq:
+                        raise ValueError(f"checkpoint key {k}: these are {kind.upper()} experts, "
+                                         f"load them with --expert-quantization {kind}")
+                elif eq is not None and kind == "fp8":
+                    pass  # an fp8 attention projection next to fp8 experts: dequantized below
+                elif kind != self.quantization:
                     raise ValueError(f"checkpoint key {k}: this is an {kind.upper()} checkpoint, "
                                      f"load it with --quantization {kind}")
         proj = lambda key: _checkpoint_proj(sd, key, self.quantization)  # noqa: E731
+        if eq is not None:
+            # only the experts are quantized: a pre-quantized attention projection becomes bf16
+            noted = []
+
+            def proj(key):  # noqa: F811
+                w = _checkpoint_proj(sd, key, eq)
+                if isinstance(w, Fp8Weight):
+                    if not noted:
+                        noted.append(key)
+                        print(f"[weights] {cfg.name}: fp8 attention projections ({key}, ...) are "
+                              f"dequantized to bf16 at load: only the experts stay fp8", flush=True)
+                    w = w.float()
+                return w
+        eproj = None if eq is None else (lambda key: _checkpoint_proj(sd, key, eq))
         cp = lambda dst, src: dst.copy_(src.to(dst.dtype))  # noqa: E731
         emb = sd["model.embed_tokens.weight"]
         n = self.vocab_end - self.vocab_start
@@ -444,7 +500,10 @@ class DecoderLM:
                 cp(lw.q_norm, sd[p + "self_attn.q_norm.weight"])
                 cp(lw.k_norm, sd[p + "self_attn.k_norm.weight"])
             if lw.moe is not None:
-                lw.moe.load_state_dict(sd, p)
+                lw.moe.load_state_dict(sd, p, fp8_proj=eproj)
+                if eproj is not None:
+                    self.experts_quantized = True
+                    reserve_scratch(max(lw.moe.w13.numel(), lw.moe.w2.numel()), self.device)
             else:
                 g_ = _shard_rows(proj(p + "mlp.gate_proj"), r, tp)
                 u_ = _shard_rows(proj(p + "mlp.up_proj"), r, tp)

@@ -750,7 +750,13 @@ def fused_moe(h, w13, w2, topk_w, topk_ids, out=None):
     MFMA GEMM gathering token rows with the SwiGLU in its epilogue (csrc/kernels/
     moe_dgemm.hip) -> grouped GEMM -> deterministic gather-combine.  All buffer shapes depend
     only on (T, top_k, E), so the whole block captures in a hipGraph.
-    w13 [E, 2F, d], w2 [E, d, F]."""
+    w13 [E, 2F, d], w2 [E, d, F]: both bf16 tensors, or both Fp8Experts (ops/quant.py), which
+    run the same pipeline on the 1-byte-weight grouped GEMM (csrc/kernels/moe_qgemm.hip)."""
+    from .quant import Fp8Experts
+
+    fp8 = isinstance(w13, Fp8Experts)
+    if fp8 != isinstance(w2, Fp8Experts):
+        raise TypeError("fused_moe: w13 and w2 must both be bf16 tensors or both Fp8Experts")
     T, d = h.shape
     K = topk_ids.shape[1]
     E = w13.shape[0]
@@ -760,6 +766,8 @@ def fused_moe(h, w13, w2, topk_w, topk_ids, out=None):
     if not _native(h):
         out.copy_(ref.fused_moe(h, w13, w2, topk_w, topk_ids))
         return out
+    if fp8:
+        return _fused_moe_fp8(h, w13, w2, topk_w, topk_ids, out)
     n = T * K
     bm = moe_tile_rows(n, E)
     cap = moe_capacity(n, E, bm)
@@ -784,6 +792,49 @@ def fused_moe(h, w13, w2, topk_w, topk_ids, out=None):
                              _moe_pf(F), bm)
     torch.ops.akap.moe_combine(y2, topk_w.contiguous(), inv, out)
     return out
+
+
+def _fused_moe_fp8(h, w13, w2, topk_w, topk_ids, out):
+    """fused_moe's GPU pipeline over Fp8Experts: the same align / tile rows / split choice /
+    buffers / combines, both grouped GEMMs on moe_qgemm."""
+    T, d = h.shape
+    K = topk_ids.shape[1]
+    E = w13.shape[0]
+    F = w2.shape[2]
+    n = T * K
+    bm = moe_tile_rows(n, E)
+    cap = moe_capacity(n, E, bm)
+    tiles = cap // bm
+    dev = h.device
+    inv = torch.empty(n, dtype=torch.int32, device=dev)
+    tile_expert = torch.empty(tiles, dtype=torch.int32, device=dev)
+    sorted_ids, _, _ = moe_align(topk_ids, E, bm, inv=inv, tile_expert=tile_expert)
+    act = torch.empty(cap, F, dtype=h.dtype, device=dev)
+    torch.ops.akap.moe_qgemm(act, h, w13.q, w13.scale, sorted_ids, tile_expert, n, K, True, True,
+                             _moe_qpf(d), bm)
+    S = moe_down_splitk(n, E, bm, F)
+    if S > 1:
+        P = torch.empty(S * cap * d, dtype=torch.float32, device=dev)
+        torch.ops.akap.moe_qgemm(P, act, w2.q, w2.scale, sorted_ids, tile_expert, n, K, False,
+                                 False, _moe_qpf(F // S), bm, S)
+        torch.ops.akap.moe_combine_split(P, topk_w.contiguous(), inv, out, S, cap)
+        return out
+    y2 = torch.empty(cap, d, dtype=h.dtype, device=dev)
+    torch.ops.akap.moe_qgemm(y2, act, w2.q, w2.scale, sorted_ids, tile_expert, n, K, False, False,
+                             _moe_qpf(F), bm)
+    torch.ops.akap.moe_combine(y2, topk_w.contiguous(), inv, out)
+    return out
+
+
+def _moe_qpf(K: int) -> int:
+    """Deepest load ring of moe_qgemm (128-deep steps, the last maybe half) the reduction
+    depth allows."""
+    if K % 64:
+        raise ValueError(f"MoE GEMM needs K % 64 == 0, got {K}")
+    steps = (K + 127) // 128
+    for pf in (4, 2, 1):
+        if steps % pf == 0:
+            return pf
 
 
 def moe_down_splitk(n: int, num_experts: int, bm: int, F: int) -> int:

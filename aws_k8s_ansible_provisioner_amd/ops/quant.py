@@ -9,6 +9,10 @@ accumulated in fp32.  Activations stay bf16: every e4m3 value is exact in bf16, 
 kernel (csrc/kernels/qgemm.hip) streams 1-byte weights, widens them in registers and runs the
 bf16 MFMA; the scale multiplies the fp32 accumulators.
 
+``Fp8Experts(q, scale)`` is the same for the experts of an MoE layer: ``q`` uint8 [E, N, K],
+``scale`` fp32 [E, N]; expert e follows the contract above with scale[e] (the grouped kernel is
+csrc/kernels/moe_qgemm.hip).
+
 ``Mxfp4Weight(q, scale)``: ``q`` uint8 [N, K/2] holding two e2m1 codes per byte (element 2j in
 the low nibble of byte j, element 2j+1 in the high nibble: torch.float4_e2m1fn_x2's packing),
 ``scale`` uint8 [N, K/32], one e8m0 code s (value 2^(s-127), 2 <= s <= 252) per 32 elements
@@ -111,8 +115,119 @@ def quantize_fp8(w: torch.Tensor) -> Fp8Weight:
     return Fp8Weight(q.view(torch.uint8), scale)
 
 
+class Fp8Experts:
+    """The FP8 weights of a group of MoE experts, [E, N, K]: ``q`` uint8 e4m3fn codes (never a
+    NaN code), ``scale`` fp32 [E, N], one value per expert and output channel.  Per expert e
+
+        Y[r, n] = bf16(scale[e, n] * sum_k float(X[r, k]) * float(q[e, n, k]))
+
+    accumulated in fp32 (csrc/kernels/moe_qgemm.hip).  ``w[e]`` is expert e's Fp8Weight, so
+    code written for a bf16 [E, N, K] tensor that reads ``w[e].float()`` works unchanged."""
+
+    __slots__ = ("q", "scale")
+
+    def __init__(self, q: torch.Tensor, scale: torch.Tensor):
+        if q.dtype == torch.float8_e4m3fn:
+            q = q.view(torch.uint8)
+        if q.dtype != torch.uint8 or q.dim() != 3:
+            raise ValueError("Fp8Experts: q must be a 3-D uint8 / float8_e4m3fn tensor [E, N, K]")
+        if scale.dtype != torch.float32 or tuple(scale.shape) != tuple(q.shape[:2]):
+            raise ValueError("Fp8Experts: scale must be fp32 [E, N]")
+        self.q = q.contiguous()
+        self.scale = scale.contiguous()
+
+    @property
+    def shape(self) -> torch.Size:
+        return self.q.shape
+
+    @property
+    def device(self) -> torch.device:
+        return self.q.device
+
+    @property
+    def is_cuda(self) -> bool:
+        return self.q.is_cuda
+
+    @property
+    def dtype(self) -> torch.dtype:
+        return torch.float8_e4m3fn
+
+    def dim(self) -> int:
+        return 3
+
+    def numel(self) -> int:
+        return self.q.numel()
+
+    @property
+    def nbytes(self) -> int:
+        """E * N * K code bytes + 4 * E * N scale bytes."""
+        return self.q.numel() + 4 * self.scale.numel()
+
+    def float(self) -> torch.Tensor:
+        """The dequantized fp32 tensor float(q) * scale[:, :, None] (exact)."""
+        return self.q.view(torch.float8_e4m3fn).float() * self.scale[:, :, None]
+
+    def flat(self) -> Fp8Weight:
+        """All experts' channels as one [E * N, K] Fp8Weight (a view: the dequantizer's input)."""
+        E, N, K = self.q.shape
+        return Fp8Weight(self.q.view(E * N, K), self.scale.view(E * N))
+
+    def __getitem__(self, idx):
+        """w[e] -> expert e's Fp8Weight; w[a:b] -> the experts a..b (expert parallelism);
+        w[:, :, a:b] / w[:, a:b] -> column / channel slices of every expert (tensor
+        parallelism; a column slice keeps the scales, as Fp8Weight does)."""
+        idx = idx if isinstance(idx, tuple) else (idx,)
+        if len(idx) > 3:
+            raise IndexError("Fp8Experts: at most 3 indices")
+        ex, rows, cols = tuple(idx) + (slice(None),) * (3 - len(idx))
+        if not (isinstance(rows, slice) and isinstance(cols, slice)):
+            raise TypeError("Fp8Experts supports channel and column slices only")
+        if isinstance(ex, int):
+            return Fp8Weight(self.q[ex, rows, cols], self.scale[ex, rows])
+        if not isinstance(ex, slice):
+            raise TypeError("Fp8Experts: the expert index is an int or a slice")
+        return Fp8Experts(self.q[ex, rows, cols], self.scale[ex, rows])
+
+    def to(self, device) -> "Fp8Experts":
+        return Fp8Experts(self.q.to(device), self.scale.to(device))
+
+    def __repr__(self) -> str:
+        return f"Fp8Experts(shape={tuple(self.shape)}, device={self.device})"
+
+
+@torch.no_grad()
+def quantize_fp8_experts(w: torch.Tensor) -> Fp8Experts:
+    """quantize_fp8's rule per expert and output channel of w [E, N, K]."""
+    if w.dim() != 3:
+        raise ValueError("quantize_fp8_experts: 3-D weight [E, N, K]")
+    E, N, K = w.shape
+    q = torch.empty(E, N, K, dtype=torch.uint8, device=w.device)
+    scale = torch.empty(E, N, dtype=torch.float32, device=w.device)
+    for e in range(E):  # one expert's fp32 temporaries at a time
+        f = quantize_fp8(w[e])
+        q[e].copy_(f.q)
+        scale[e].copy_(f.scale)
+    return Fp8Experts(q, scale)
+
+
+def dequant_fp8_experts(w: Fp8Experts) -> torch.Tensor:
+    """bf16(float(q) * scale) of all experts as a [E, N, K] view of the shared scratch (GPU:
+    the dequant_fp8 kernel, bit-exact; stream-ordered like every other use of the scratch,
+    never inside a captured region) or a new tensor (CPU)."""
+    if not w.is_cuda:
+        return w.float().to(torch.bfloat16)
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("fp8 experts are not dequantized inside a captured region")
+    from . import load_native
+
+    load_native(required=True)
+    if w.shape[2] % 16:
+        raise ValueError(f"fp8 experts {tuple(w.shape)}: K must be a multiple of 16")
+    return _dequant_to_scratch(w.flat()).view(w.shape)
+
+
 # ------------------------------------------------------------------ MXFP4
-MX_BLOCK = 32                      # elements along K that share one e8m0 scale
+MX_BLOCK = 32                     # elements along K that share one e8m0 scale
 MX_SCALE_MIN, MX_SCALE_MAX = 2, 252  # accepted e8m0 codes: 0.5 * 2^e and 6 * 2^e normal in bf16
 _E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
 

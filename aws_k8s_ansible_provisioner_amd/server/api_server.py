@@ -641,6 +641,11 @@ def make_parser() -> argparse.ArgumentParser:
                          "mxfp4: e2m1 weights with one e8m0 scale per 32 elements along K, same "
                          "scope (loads uint8 weight + weight_scale checkpoints). "
                          "Default: AKAP_QUANTIZATION, else none")
+    ap.add_argument("--expert-quantization", default=None, choices=["none", "fp8"],
+                    help="MoE models: fp8 = per-(expert, channel) e4m3 expert weights, everything "
+                         "else bf16 (loads FP8 expert checkpoints, quantizes bf16 experts at "
+                         "start-up); --quantization stays none on an MoE model. "
+                         "Default: AKAP_EXPERT_QUANTIZATION, else none")
     ap.add_argument("--otlp-traces-endpoint", default=None,
                     help="OTLP/HTTP collector (e.g. http://otel-collector:4318); also read "
                          "from OTEL_EXPORTER_OTLP_TRACES_ENDPOINT")
@@ -665,7 +670,8 @@ def engine_config_from_args(a) -> EngineConfig:
         enforce_eager=a.enforce_eager, tensor_parallel_size=a.tensor_parallel_size, seed=a.seed,
         device=a.device, load_format=a.load_format, weights_path=a.weights_path,
         chat_template=a.chat_template, kv_role=a.kv_role, kv_cache_dtype=a.kv_cache_dtype,
-        quantization=getattr(a, "quantization", None))
+        quantization=getattr(a, "quantization", None),
+        expert_quantization=getattr(a, "expert_quantization", None))
 
 
 def pd_group_id() -> str:
