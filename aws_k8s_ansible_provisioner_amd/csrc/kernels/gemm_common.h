@@ -1,5 +1,5 @@
 // Device helpers shared by the GEMM kernels (gemm / dgemm / gdgemm / kgemm / wgemm / qgemm /
-// pgemm / moe_dgemm / moe_qgemm): LDS swizzle and LDS-DMA staging, counted waits, the epilogue arithmetic
+// pgemm / moe_dgemm / moe_qgemm / moe_q4gemm): LDS swizzle and LDS-DMA staging, counted waits, the epilogue arithmetic
 // whose rounding order is a contract with the CPU reference, and the split-K ticket step.
 #pragma once
 
@@ -34,6 +34,23 @@ __device__ __forceinline__ void wait_vm() {
 }
 
 __device__ __forceinline__ float silu_bf(float g) { return bf2f(f2bf(g / (1.f + __expf(-g)))); }
+
+// ---- MXFP4 weights: q4gemm.hip, moe_q4gemm.hip ------------------------------------------------
+// LDS rows of 64 B = 4 chunks of 16 B (128 packed e2m1 codes): the 64-B-row swizzle of
+// qgemm.hip / wgemm.hip ww_swz.  Returns the 16-B unit index.
+__device__ __forceinline__ int q4swz_g(int row) { return (0x1320 >> (4 * ((row >> 2) & 3))) & 3; }
+__device__ __forceinline__ int q4swz_w(int row, int c) { return row * 4 + (c ^ q4swz_g(row)); }
+
+// 8 e2m1 codes (element e in bits [4e, 4e + 4)) times `scale` (a power of two) -> 8 bf16, exact
+__device__ __forceinline__ bf16x8 fp4x8_to_bf16x8(uint32_t v, float scale) {
+  const bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, scale, 0);
+  const bf16x2 b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, scale, 1);
+  const bf16x2 c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, scale, 2);
+  const bf16x2 d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, scale, 3);
+  return bf16x8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
+}
+// e8m0 code (2..252) -> 2^(code - 127)
+__device__ __forceinline__ float e8m0_to_f32(uint32_t code) { return __uint_as_float(code << 23); }
 
 // ---- per-channel scaled (FP8-weight) epilogues: moe_qgemm.hip ---------------------------------
 // The rounding order, a contract with the CPU reference (ops/quant.py): the scale of the weight

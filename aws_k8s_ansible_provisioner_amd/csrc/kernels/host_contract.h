@@ -205,6 +205,19 @@ inline bool moe_qgemm_supported(int N, int K, int pf, int silu, int splitk) {
   return silu ? N % 32 == 0 : N % 8 == 0;
 }
 
+// ---- moe_q4gemm.hip: the MXFP4-expert form; moe_qgemm's MQBK-deep ring step and half step.
+// A scale row is K / 32 bytes and a step reads 4 of them (a half step 2), so K % MQBK == 0;
+// with that, pf = 1 takes every (N, K, silu, splitk) that moe_dgemm_supported takes for some
+// pf ----
+inline bool moe_q4gemm_supported(int N, int K, int pf, int silu, int splitk) {
+  if (pf != 1 && pf != 2 && pf != 4) return false;
+  if (N <= 0 || K <= 0 || K % MQBK) return false;
+  if (splitk < 1 || K % splitk || (K / splitk) % MBK) return false;
+  if (((K / splitk + MQBK - 1) / MQBK) % pf) return false;
+  if (silu && splitk > 1) return false;
+  return silu ? N % 32 == 0 : N % 8 == 0;
+}
+
 inline bool moe_router_topk_supported(int E, int d) {
   return E >= 1 && E <= kRouterMaxE && d % 8 == 0;
 }

@@ -246,6 +246,17 @@ void launch_moe_qgemm(const void* A, const void* Wq, const float* scale, void* Y
                       int pf, int bm, int splitk, float* partials, bool nt_weights,
                       hipStream_t s);
 
+// ---- moe_q4gemm.hip ----
+// The same grouped GEMM over MXFP4 expert weights: Wq uint8 [E, N, K/2] (two OCP e2m1 codes per
+// byte, element 2j in the low nibble), scale uint8 [E, N, K/32] (e8m0 codes 2..252); the block
+// scale is applied at the widening, the epilogues are moe_dgemm's.  K % 128 == 0.  No workspace,
+// no cross-workgroup state.
+void launch_moe_q4gemm(const void* A, const void* Wq, const void* scale, void* Y,
+                       const int32_t* sorted_ids, const int32_t* tile_expert, int max_tiles,
+                       int n_flat, int topk, int N, int K, int lda, int ldy, int gather, int silu,
+                       int pf, int bm, int splitk, float* partials, bool nt_weights,
+                       hipStream_t s);
+
 // ---- moe.hip ----
 void launch_moe_topk_softmax(const void* logits, int ld, int E, int K, float* topk_w,
                              int32_t* topk_ids, int T, int renormalize, hipStream_t s);

@@ -34,26 +34,11 @@
 
 namespace akap {
 
-// the 64-B-row swizzle of qgemm.hip / wgemm.hip ww_swz
-__device__ __forceinline__ int q4swz_g(int row) { return (0x1320 >> (4 * ((row >> 2) & 3))) & 3; }
-__device__ __forceinline__ int q4swz_w(int row, int c) { return row * 4 + (c ^ q4swz_g(row)); }
-
 // LDS-DMA, 4 B per lane from g to lds_wave_base + 4 * lane
 __device__ __forceinline__ void glds4(const void* g, void* lds_wave_base) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
                                    (__attribute__((address_space(3))) void*)lds_wave_base, 4, 0, 0);
 }
-
-// 8 e2m1 codes (element e in bits [4e, 4e + 4)) times `scale` (a power of two) -> 8 bf16, exact
-__device__ __forceinline__ bf16x8 fp4x8_to_bf16x8(uint32_t v, float scale) {
-  const bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, scale, 0);
-  const bf16x2 b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, scale, 1);
-  const bf16x2 c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, scale, 2);
-  const bf16x2 d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, scale, 3);
-  return bf16x8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
-}
-// e8m0 code (2..252) -> 2^(code - 127)
-__device__ __forceinline__ float e8m0_to_f32(uint32_t code) { return __uint_as_float(code << 23); }
 
 template <int MI, int NJ, int NS>
 __global__ __launch_bounds__(256, 1) void q4gemm_kernel(Q4GemmArgs p) {

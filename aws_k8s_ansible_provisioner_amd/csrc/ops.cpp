@@ -758,6 +758,52 @@ void moe_qgemm(Tensor out, Tensor a, Tensor wq, Tensor scale, Tensor sorted_ids,
                          cur_stream());
 }
 
+// moe_dgemm over MXFP4 expert weights (csrc/kernels/moe_q4gemm.hip): wq uint8 [E, N, K/2] packed
+// e2m1 codes, scale uint8 [E, N, K/32] e8m0 codes; out as moe_dgemm's.
+void moe_q4gemm(Tensor out, Tensor a, Tensor wq, Tensor scale, Tensor sorted_ids,
+                Tensor tile_expert, int64_t n_flat, int64_t topk, bool gather, bool silu,
+                int64_t pf, int64_t bm, int64_t splitk) {
+  const OpArgs o = on_gpu("moe_q4gemm", a, "a");
+  TORCH_CHECK(wq.dim() == 3 && a.dim() == 2,
+              "moe_q4gemm: a [rows, K], expert weights wq [E, N, K/2]");
+  const int64_t E = wq.size(0);
+  const int N = wq.size(1), K = 2 * wq.size(2);
+  TORCH_CHECK(K % akap::MXBLK == 0 && scale.dim() == 3 && scale.size(0) == E &&
+                  scale.size(1) == N && scale.size(2) == K / akap::MXBLK,
+              "moe_q4gemm: scale must be [E, N, K/32]");
+  TORCH_CHECK(a.size(1) == K, "moe_q4gemm: a width != K");
+  TORCH_CHECK(akap::moe_q4gemm_supported(N, K, pf, silu, splitk),
+              "moe_q4gemm: unsupported N/K/pf/split");
+  TORCH_CHECK(a.stride(0) % 8 == 0, "moe_q4gemm: 16-byte aligned rows");
+  TORCH_CHECK(bm == 32 || bm == 64, "moe_q4gemm: tile rows 32 | 64");
+  TORCH_CHECK(topk >= 1 && n_flat >= 0, "moe_q4gemm: topk >= 1, n_flat >= 0");
+  const int max_tiles = tile_expert.numel();
+  const int64_t rows = (int64_t)max_tiles * bm;
+  // split-K: out is the fp32 partials [splitk, rows, N]
+  float* partials = splitk > 1 ? o.ptr<float>(out, "out", splitk * rows * N) : nullptr;
+  void* y = splitk > 1 ? nullptr : o.bf16(out, "out");
+  TORCH_CHECK(splitk > 1 || (out.dim() == 2 && out.size(1) == (silu ? N / 2 : N)),
+              "moe_q4gemm: out width");
+  TORCH_CHECK(splitk > 1 || out.size(0) >= rows, "moe_q4gemm: out rows must cover all tiles");
+  TORCH_CHECK(gather ? a.size(0) * topk >= n_flat : a.size(0) >= rows,
+              "moe_q4gemm: a rows must cover all tiles (gather: all n_flat / topk tokens)");
+  // the non-temporal policy of moe_dgemm (one row tile per expert streams its weights once)
+  static const int nt_env = [] {
+    const char* e = std::getenv("AKAP_MOE_NT");
+    return e ? std::atoi(e) : -1;
+  }();
+  const bool ntw = nt_env >= 0 ? nt_env != 0 : (bm == 64 && n_flat <= 40 * E);
+  akap::launch_moe_q4gemm(o.bf16(a, "a", 0, kLastContig | kAlign16),
+                          o.ptr<uint8_t>(wq, "wq", E * N * (K / 2), kContig | kAlign16),
+                          o.ptr<uint8_t>(scale, "scale", E * N * (K / akap::MXBLK),
+                                         kContig | kAlign16),
+                          y, o.ptr<int32_t>(sorted_ids, "sorted_ids", rows),
+                          o.ptr<int32_t>(tile_expert, "tile_expert"), max_tiles, n_flat, topk, N,
+                          K, a.stride(0), splitk > 1 ? N : out.stride(0), gather ? 1 : 0,
+                          silu ? 1 : 0, (int)pf, (int)bm, (int)splitk, partials, ntw,
+                          cur_stream());
+}
+
 void moe_combine_split(Tensor partials, Tensor wts, Tensor inv, Tensor out, int64_t splitk,
                        int64_t rows) {
   const OpArgs a = on_gpu("moe_combine_split", partials, "partials");
@@ -1336,6 +1382,10 @@ TORCH_LIBRARY(akap, m) {
       "Tensor tile_expert, int n_flat, int topk, bool gather, bool silu, int pf, int bm=32, "
       "int splitk=1) -> ()");
   m.def(
+      "moe_q4gemm(Tensor(a!) out, Tensor a, Tensor wq, Tensor scale, Tensor sorted_ids, "
+      "Tensor tile_expert, int n_flat, int topk, bool gather, bool silu, int pf, int bm=32, "
+      "int splitk=1) -> ()");
+  m.def(
       "moe_combine_split(Tensor partials, Tensor wts, Tensor inv, Tensor(a!) out, int splitk, "
       "int rows) -> ()");
   m.def("kv_gather(Tensor cache, Tensor block_ids, Tensor(a!) out) -> ()");
@@ -1389,6 +1439,7 @@ TORCH_LIBRARY_IMPL(akap, CUDA, m) {
   m.impl("moe_combine", &moe_combine);
   m.impl("moe_dgemm", &moe_dgemm);
   m.impl("moe_qgemm", &moe_qgemm);
+  m.impl("moe_q4gemm", &moe_q4gemm);
   m.impl("moe_combine_split", &moe_combine_split);
   m.impl("car_all_reduce", &car_all_reduce);
   m.impl("l2_prefetch", &l2_prefetch);

@@ -88,6 +88,7 @@ static void bind_contract(py::module_ m) {
   });
   m.def("moe_dgemm_supported", &moe_dgemm_supported);
   m.def("moe_qgemm_supported", &moe_qgemm_supported);
+  m.def("moe_q4gemm_supported", &moe_q4gemm_supported);
   m.def("moe_router_topk_supported", &moe_router_topk_supported);
   // -> (supported, family 0 ring | 1 lds | 2 pgemm_sk, combines in launch, ws floats, ticket ints)
   m.def("dgemm_contract", [](int M, int N, int K, int pro, int epi, int splitk, int pf, int bn,

@@ -46,17 +46,24 @@ class EngineConfig:
     # "none" = bf16.  None takes AKAP_QUANTIZATION from the environment
     # (unset: bf16); an explicit value, "none" included, wins over the variable
     quantization: Optional[str] = None
-    # MoE expert weights only: "fp8" = per-(expert, channel) e4m3fn expert weights (attention
-    # projections, router, embedding, LM head and norms stay bf16; `quantization` must be none
-    # on an MoE model); "none" = bf16.  None takes AKAP_EXPERT_QUANTIZATION from the environment
+    # MoE expert weights only: "fp8" = per-(expert, channel) e4m3fn expert weights, "mxfp4" =
+    # e2m1 expert weights with one e8m0 scale per 32 elements along K (attention projections,
+    # router, embedding, LM head and norms stay bf16; `quantization` must be none on an MoE
+    # model); "none" = bf16.  None takes AKAP_EXPERT_QUANTIZATION from the environment
     # (unset: bf16); an explicit value, "none" included, wins over the variable
     expert_quantization: Optional[str] = None
 
     def __post_init__(self) -> None:
+        # a value the variable cannot mean is an error of the deployment whether or not this
+        # config reads it: a field that overrides it must not hide it
+        env = os.environ.get("AKAP_EXPERT_QUANTIZATION") or None
+        if env not in (None, "none", "fp8", "mxfp4"):
+            raise ValueError(f"expert_quantization: AKAP_EXPERT_QUANTIZATION must be none, fp8 "
+                             f"or mxfp4, got {env!r}")
         if self.expert_quantization is None:
-            self.expert_quantization = os.environ.get("AKAP_EXPERT_QUANTIZATION") or None
-        if self.expert_quantization not in (None, "none", "fp8"):
-            raise ValueError(f"expert_quantization must be none or fp8, "
+            self.expert_quantization = env
+        if self.expert_quantization not in (None, "none", "fp8", "mxfp4"):
+            raise ValueError(f"expert_quantization must be none, fp8 or mxfp4, "
                              f"got {self.expert_quantization!r}")
         if self.quantization is None:
             self.quantization = os.environ.get("AKAP_QUANTIZATION") or None

@@ -79,13 +79,17 @@ class ModelRunner:
             self.log(f"[runner] {ecfg.quantization} weights: "
                      f"{self.model.weight_bytes() / 2**30:.2f} GiB/rank "
                      f"(bf16 {bf16_gib:.2f} GiB; embedding, LM head and norms stay bf16)")
-        if ecfg.expert_quantization == "fp8":
-            # same place as above: the freed bf16 experts count for the KV cache
-            self.model.quantize_experts_fp8()
+        if ecfg.expert_quantization in ("fp8", "mxfp4"):
+            # same place as above: the freed bf16 experts count for the KV cache, and the
+            # dequantization scratch is reserved before the cache is sized
+            if ecfg.expert_quantization == "mxfp4":
+                self.model.quantize_mxfp4_experts()
+            else:
+                self.model.quantize_experts_fp8()
             bf16_gib = self.model.weight_bytes(as_bf16=True) / 2**30
             if self.is_gpu:
                 torch.cuda.empty_cache()
-            self.log(f"[runner] fp8 expert weights: "
+            self.log(f"[runner] {ecfg.expert_quantization} expert weights: "
                      f"{self.model.weight_bytes() / 2**30:.2f} GiB/rank "
                      f"(bf16 {bf16_gib:.2f} GiB; attention projections, router, embedding, "
                      f"LM head and norms stay bf16)")

@@ -39,8 +39,9 @@ import torch
 import torch.nn.functional as F
 
 from .. import ops
-from ..ops.quant import (Fp8Experts, Fp8Weight, dequant_fp8_experts, quantize_fp8,
-                         quantize_fp8_experts)
+from ..ops.quant import (Fp8Experts, Fp8Weight, Mxfp4Experts, Mxfp4Weight, QuantExperts,
+                         dequant_experts, quantize_fp8, quantize_fp8_experts, quantize_mxfp4,
+                         quantize_mxfp4_experts)
 from ..parallel import comm
 from ..parallel.state import ParallelState
 
@@ -134,27 +135,50 @@ class MoEBlock:
 
     @property
     def quantized(self) -> bool:
-        return isinstance(self.w13, Fp8Experts)
+        return isinstance(self.w13, QuantExperts)
 
     @torch.no_grad()
     def quantize_fp8(self) -> None:
         """Replace this rank's expert weights (its local experts in ep mode, its F shard in tp
         mode) by Fp8Experts, one tensor at a time: each bf16 tensor is dropped before the next
         quantized one is made.  The router stays bf16."""
+        self._quantize(Fp8Experts, quantize_fp8_experts)
+
+    def check_mxfp4_shapes(self) -> None:
+        """The 4-bit grouped GEMM (csrc/kernels/moe_q4gemm.hip) reads 4 scale codes per weight
+        row and 128-deep step: both reduction depths, d and this rank's F shard, must be
+        multiples of 128 (which also keeps a TP shard on whole 32-element scale blocks)."""
+        d, fl = self.cfg.hidden_size, self.f_local
+        if d % 128 or fl % 128:
+            raise ValueError(f"{self.cfg.name}: mxfp4 experts need hidden_size ({d}) and the "
+                             f"intermediate size per rank ({fl} = {self.cfg.intermediate_size} / "
+                             f"{self.cfg.intermediate_size // fl}) to be multiples of 128; use "
+                             f"expert parallelism (AKAP_MOE_MODE=ep), a smaller tensor-parallel "
+                             f"size, or fp8 experts")
+
+    @torch.no_grad()
+    def quantize_mxfp4(self) -> None:
+        """quantize_fp8 for Mxfp4Experts (the OCP MX rule per 32-block, quantize_mxfp4)."""
+        self.check_mxfp4_shapes()
+        self._quantize(Mxfp4Experts, quantize_mxfp4_experts)
+
+    def _quantize(self, kind, quantizer) -> None:
         for name in ("w13", "w2"):
             w = getattr(self, name)
-            if not isinstance(w, Fp8Experts):
+            if isinstance(w, QuantExperts) and not isinstance(w, kind):
+                raise ValueError(f"{name} is already {type(w).__name__}")
+            if not isinstance(w, kind):
                 setattr(self, name, None)
-                q = quantize_fp8_experts(w)
+                q = quantizer(w)
                 del w
                 setattr(self, name, q)
 
     def weight_bytes(self, as_bf16: bool = False) -> int:
-        """The router and plain experts at 2 bytes per element; Fp8Experts at their nbytes
-        (codes + fp32 scales), or at 2 bytes per element with as_bf16."""
+        """The router and plain experts at 2 bytes per element; Fp8Experts / Mxfp4Experts at
+        their nbytes (codes + scales), or at 2 bytes per element with as_bf16."""
         n = 2 * self.router.numel()
         for w in (self.w13, self.w2):
-            n += w.nbytes if isinstance(w, Fp8Experts) and not as_bf16 else 2 * w.numel()
+            n += w.nbytes if isinstance(w, QuantExperts) and not as_bf16 else 2 * w.numel()
         return n
 
     def _hf_names(self, prefix: str, e: int) -> tuple:
@@ -203,13 +227,48 @@ class MoEBlock:
                                              proj(key(names(e)[2]))[fs]]))
         fill("w2", d, fl, lambda e: q8([proj(key(names(e)[3]))[:, fs]]))
 
-    def load_state_dict(self, sd: dict, prefix: str, fp8_proj=None) -> None:
+    def _load_mxfp4(self, prefix: str, proj) -> None:
+        """Expert weights of a checkpoint as Mxfp4Experts.  proj(key) is the projection
+        `key`.weight: an Mxfp4Weight for packed uint8 [N, K/2] codes with uint8 `weight_scale`
+        [N, K/32] (kept bit for bit; gate and up are concatenated along N with their scales; a
+        TP shard slices F on whole scale blocks), else a plain tensor, quantized here."""
+        self.check_mxfp4_shapes()
+        r = self.ps.tp_rank
+        d, fl = self.cfg.hidden_size, self.f_local
+        fs = slice(None) if self.mode == "ep" else slice(r * fl, (r + 1) * fl)
+
+        def q4(parts: list) -> Mxfp4Weight:
+            if all(isinstance(p, Mxfp4Weight) for p in parts):
+                return Mxfp4Weight(torch.cat([p.q for p in parts], 0),
+                                   torch.cat([p.scale for p in parts], 0), check=False)
+            return quantize_mxfp4(torch.cat([p.float() for p in parts], 0).to(self.device))
+
+        def fill(name: str, N: int, K: int, expert) -> None:
+            setattr(self, name, None)  # drop the old tensor before the new one is resident
+            q = torch.empty(self.e_local, N, K // 2, dtype=torch.uint8, device=self.device)
+            s = torch.empty(self.e_local, N, K // 32, dtype=torch.uint8, device=self.device)
+            for j in range(self.e_local):
+                w = expert(self.e0 + j)
+                if tuple(w.shape) != (N, K):
+                    raise ValueError(f"{prefix}expert {self.e0 + j} {name}: checkpoint shape "
+                                     f"{tuple(w.shape)} != model {(N, K)}")
+                q[j].copy_(w.q)
+                s[j].copy_(w.scale)
+            setattr(self, name, Mxfp4Experts(q, s, check=False))  # each part was checked
+
+        key = lambda n: n[:-len(".weight")]  # noqa: E731
+        names = lambda e: self._hf_names(prefix, e)  # noqa: E731
+        fill("w13", 2 * fl, d, lambda e: q4([proj(key(names(e)[1]))[fs],
+                                             proj(key(names(e)[2]))[fs]]))
+        fill("w2", d, fl, lambda e: q4([proj(key(names(e)[3]))[:, fs]]))
+
+    def load_state_dict(self, sd: dict, prefix: str, fp8_proj=None, kind: str = "fp8") -> None:
         """fp8_proj: with expert quantization on, the checkpoint accessor (DecoderLM) through
-        which the experts are loaded as Fp8Experts."""
+        which the experts are loaded as Fp8Experts or (kind "mxfp4") Mxfp4Experts."""
         r, tp = self.ps.tp_rank, self.ps.tp_size
         self.router.copy_(sd[self._hf_names(prefix, 0)[0]])
         if fp8_proj is not None:
-            self._load_fp8(prefix, fp8_proj)
+            (self._load_mxfp4 if kind == "mxfp4" else self._load_fp8)(prefix, fp8_proj)
             return
         for j in range(self.e_local):
             e = self.e0 + j
@@ -229,6 +288,12 @@ class MoEBlock:
         sd = {self._hf_names(prefix, 0)[0]: self.router.clone()}
         for e in range(self.E):
             _, n1, n3, n2 = self._hf_names(prefix, e)
+            if isinstance(self.w13, Mxfp4Experts):
+                # packed uint8 codes + uint8 e8m0 weight_scale [N, K/32], the dense MXFP4 form
+                for n, w in ((n1, self.w13[e][:Fn]), (n3, self.w13[e][Fn:]), (n2, self.w2[e])):
+                    sd[n] = w.q.clone()
+                    sd[n[:-len(".weight")] + ".weight_scale"] = w.scale.clone()
+                continue
             if self.quantized:
                 # float8_e4m3fn codes + [N, 1] fp32 weight_scale, as DecoderLM.hf_state_dict
                 for n, w in ((n1, self.w13[e][:Fn]), (n3, self.w13[e][Fn:]), (n2, self.w2[e])):
@@ -337,7 +402,7 @@ class MoEBlock:
         store: deterministic, no float atomics), or with sorted_out as (expert-sorted rows,
         order) for a caller that gathers them itself."""
         if self.quantized and not x.is_cuda:
-            # CPU reference path of FP8 experts: the exact contract (ref.fused_moe dequantizes
+            # CPU reference path of FP8 / MXFP4 experts: the exact contract (ref.fused_moe dequantizes
             # exactly), every row one (token, expert) pair of weight 1
             xs = x if src is None else x[src]
             ones = torch.ones(xs.shape[0], 1, dtype=torch.float32, device=x.device)
@@ -357,17 +422,18 @@ class MoEBlock:
         offs = torch.searchsorted(ks, torch.arange(el, device=ks.device, dtype=ks.dtype),
                                   right=True).to(torch.int32)
         xs = x[order if src is None else src[order]]
-        # FP8 experts: each tensor is dequantized (dequant_fp8 kernel, bit-exact) into the shared
+        # FP8 / MXFP4 experts: each tensor is dequantized (dequant_fp8 / dequant_mxfp4 kernel,
+        # bit-exact) into the shared
         # scratch right before the grouped GEMM that reads it; the w2 view reuses the bytes of
         # the w13 view in stream order, like the dense layers' scratch reuse
-        w13 = dequant_fp8_experts(self.w13) if self.quantized else self.w13
+        w13 = dequant_experts(self.w13) if self.quantized else self.w13
         if ops.use_pgemm(xs, w13.shape[1], silu=True, grouped=True):
             # hand-written grouped GEMM with SwiGLU in its epilogue (csrc/kernels/pgemm.hip)
             a = ops.pgemm(xs, w13, silu=True, offs=offs)
         else:
             a = ops.silu_and_mul(torch._grouped_mm(xs, w13.transpose(1, 2), offs=offs))
         del w13
-        w2 = dequant_fp8_experts(self.w2) if self.quantized else self.w2
+        w2 = dequant_experts(self.w2) if self.quantized else self.w2
         if ops.use_pgemm(a, w2.shape[1], grouped=True):
             y = ops.pgemm(a, w2, offs=offs)
         else:

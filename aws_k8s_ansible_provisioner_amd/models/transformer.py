@@ -84,7 +84,7 @@ def _shard_cols(w, rank: int, size: int):
 
 PROJECTIONS = ("w_qkv", "w_o", "w_gate_up", "w_down")
 QUANTIZATIONS = (None, "fp8", "mxfp4")
-EXPERT_QUANTIZATIONS = (None, "fp8")  # MoE expert weights only (Fp8Experts)
+EXPERT_QUANTIZATIONS = (None, "fp8", "mxfp4")  # MoE expert weights only (ops.quant.QuantExperts)
 _QUANTIZERS = {"fp8": quantize_fp8, "mxfp4": quantize_mxfp4}
 _FP8_BLOCK = 128  # block-scaled checkpoints: one weight_scale_inv per 128 x 128 block
 
@@ -193,15 +193,17 @@ class DecoderLM:
         if expert_quantization == "none":
             expert_quantization = None
         if expert_quantization not in EXPERT_QUANTIZATIONS:
-            raise ValueError(f"unknown expert quantization {expert_quantization!r} (none | fp8)")
+            raise ValueError(f"unknown expert quantization {expert_quantization!r} "
+                             f"(none | fp8 | mxfp4)")
         if expert_quantization is not None and not cfg.is_moe:
             raise ValueError(f"{cfg.name}: expert quantization set on a dense model (no experts); "
                              f"use --quantization")
-        # "fp8": load_state_dict loads the experts as Fp8Experts (pre-quantized kept bit for bit,
-        # plain ones quantized); a model built from random weights is quantized by
-        # quantize_experts_fp8.  Everything but the experts stays bf16.
+        # "fp8" / "mxfp4": load_state_dict loads the experts as Fp8Experts / Mxfp4Experts
+        # (pre-quantized kept bit for bit, plain ones quantized); a model built from random
+        # weights is quantized by quantize_experts_fp8 / quantize_mxfp4_experts.  Everything but
+        # the experts stays bf16.
         self.expert_quantization = expert_quantization
-        self.experts_quantized = False  # the MoE blocks hold Fp8Experts
+        self.experts_quantized = False  # the MoE blocks hold Fp8Experts or Mxfp4Experts
         # "fp8" / "mxfp4": load_state_dict accepts checkpoints of that kind and quantizes plain
         # ones; a model built from random weights is quantized by quantize_fp8 / quantize_mxfp4
         self.quantization = quantization
@@ -328,7 +330,8 @@ class DecoderLM:
                     q += 2 * t.numel() if as_bf16 else t.nbytes
                 elif t is not None:
                     n += t.numel()
-            if lw.moe is not None:  # quantized experts [E, N, K]: E * N * K + 4 * E * N
+            # quantized experts [E, N, K]: E N K + 4 E N (fp8) or E N K / 2 + E N K / 32 (mxfp4)
+            if lw.moe is not None:
                 q += lw.moe.weight_bytes(as_bf16)
         return n * 2 + q
 
@@ -339,14 +342,25 @@ class DecoderLM:
         bf16 (`quantized` stays false: the dense-layer logic is untouched).  Also reserves the
         dequantization scratch the prefill path uses, sized to the largest expert tensor
         (E_local * 2F * d elements)."""
+        self._quantize_experts("fp8")
+
+    @torch.no_grad()
+    def quantize_mxfp4_experts(self) -> None:
+        """The same for MXFP4: every MoE layer's expert weights become Mxfp4Experts (e2m1 codes
+        with one e8m0 scale per 32 elements along K), on each rank's local experts or F shard,
+        which must be a multiple of 128 (MoEBlock.check_mxfp4_shapes).  The scratch is the same
+        size: it holds the dequantized bf16 tensor."""
+        self._quantize_experts("mxfp4")
+
+    def _quantize_experts(self, kind: str) -> None:
         if not self.cfg.is_moe:
             raise ValueError(f"{self.cfg.name}: a dense model has no experts to quantize")
         largest = 0
         for lw in self.layers:
             if lw.moe is not None:
-                lw.moe.quantize_fp8()
+                lw.moe.quantize_mxfp4() if kind == "mxfp4" else lw.moe.quantize_fp8()
                 largest = max(largest, lw.moe.w13.numel(), lw.moe.w2.numel())
-        self.expert_quantization = "fp8"
+        self.expert_quantization = kind
         self.experts_quantized = True
         reserve_scratch(largest, self.device)
 
@@ -368,7 +382,8 @@ class DecoderLM:
         if any(lw.moe is not None for lw in self.layers):
             raise ValueError(f"{self.cfg.name}: {kind} weight quantization covers dense models "
                              f"only (MoE experts are not quantized by it; see "
-                             f"quantize_experts_fp8 / --expert-quantization)")
+                             f"quantize_experts_fp8 / quantize_mxfp4_experts / "
+                             f"--expert-quantization)")
         largest = 0
         for lw in self.layers:
             for name in PROJECTIONS:
@@ -462,7 +477,7 @@ class DecoderLM:
                         raise ValueError(f"checkpoint key {k}: these are {kind.upper()} experts, "
                                          f"load them with --expert-quantization {kind}")
                 elif eq is not None and kind == "fp8":
-                    pass  # an fp8 attention projection next to fp8 experts: dequantized below
+                    pass  # an fp8 attention projection next to quantized experts: dequantized below
                 elif kind != self.quantization:
                     raise ValueError(f"checkpoint key {k}: this is an {kind.upper()} checkpoint, "
                                      f"load it with --quantization {kind}")
@@ -472,12 +487,14 @@ class DecoderLM:
             noted = []
 
             def proj(key):  # noqa: F811
-                w = _checkpoint_proj(sd, key, eq)
+                fp8 = sd[key + ".weight"].dtype == torch.float8_e4m3fn
+                w = _checkpoint_proj(sd, key, "fp8" if fp8 else eq)
                 if isinstance(w, Fp8Weight):
                     if not noted:
                         noted.append(key)
                         print(f"[weights] {cfg.name}: fp8 attention projections ({key}, ...) are "
-                              f"dequantized to bf16 at load: only the experts stay fp8", flush=True)
+                              f"dequantized to bf16 at load: only the experts are quantized",
+                              flush=True)
                     w = w.float()
                 return w
         eproj = None if eq is None else (lambda key: _checkpoint_proj(sd, key, eq))
@@ -500,7 +517,7 @@ class DecoderLM:
                 cp(lw.q_norm, sd[p + "self_attn.q_norm.weight"])
                 cp(lw.k_norm, sd[p + "self_attn.k_norm.weight"])
             if lw.moe is not None:
-                lw.moe.load_state_dict(sd, p, fp8_proj=eproj)
+                lw.moe.load_state_dict(sd, p, fp8_proj=eproj, kind=eq or "fp8")
                 if eproj is not None:
                     self.experts_quantized = True
                     reserve_scratch(max(lw.moe.w13.numel(), lw.moe.w2.numel()), self.device)

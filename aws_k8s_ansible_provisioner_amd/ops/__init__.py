@@ -750,13 +750,15 @@ def fused_moe(h, w13, w2, topk_w, topk_ids, out=None):
     MFMA GEMM gathering token rows with the SwiGLU in its epilogue (csrc/kernels/
     moe_dgemm.hip) -> grouped GEMM -> deterministic gather-combine.  All buffer shapes depend
     only on (T, top_k, E), so the whole block captures in a hipGraph.
-    w13 [E, 2F, d], w2 [E, d, F]: both bf16 tensors, or both Fp8Experts (ops/quant.py), which
-    run the same pipeline on the 1-byte-weight grouped GEMM (csrc/kernels/moe_qgemm.hip)."""
-    from .quant import Fp8Experts
+    w13 [E, 2F, d], w2 [E, d, F]: both bf16 tensors, or both Fp8Experts or both Mxfp4Experts
+    (ops/quant.py), which run the same pipeline on the 1-byte-weight or 4-bit-weight grouped
+    GEMM (csrc/kernels/moe_qgemm.hip, moe_q4gemm.hip)."""
+    from .quant import QuantExperts
 
-    fp8 = isinstance(w13, Fp8Experts)
-    if fp8 != isinstance(w2, Fp8Experts):
-        raise TypeError("fused_moe: w13 and w2 must both be bf16 tensors or both Fp8Experts")
+    quant = isinstance(w13, QuantExperts)
+    if type(w13) is not type(w2) and (quant or isinstance(w2, QuantExperts)):
+        raise TypeError("fused_moe: w13 and w2 must both be bf16 tensors or both Fp8Experts "
+                        "or both Mxfp4Experts")
     T, d = h.shape
     K = topk_ids.shape[1]
     E = w13.shape[0]
@@ -766,8 +768,8 @@ def fused_moe(h, w13, w2, topk_w, topk_ids, out=None):
     if not _native(h):
         out.copy_(ref.fused_moe(h, w13, w2, topk_w, topk_ids))
         return out
-    if fp8:
-        return _fused_moe_fp8(h, w13, w2, topk_w, topk_ids, out)
+    if quant:
+        return _fused_moe_quant(h, w13, w2, topk_w, topk_ids, out)
     n = T * K
     bm = moe_tile_rows(n, E)
     cap = moe_capacity(n, E, bm)
@@ -794,9 +796,14 @@ def fused_moe(h, w13, w2, topk_w, topk_ids, out=None):
     return out
 
 
-def _fused_moe_fp8(h, w13, w2, topk_w, topk_ids, out):
-    """fused_moe's GPU pipeline over Fp8Experts: the same align / tile rows / split choice /
-    buffers / combines, both grouped GEMMs on moe_qgemm."""
+def _fused_moe_quant(h, w13, w2, topk_w, topk_ids, out):
+    """fused_moe's GPU pipeline over Fp8Experts or Mxfp4Experts: the same align / tile rows /
+    split choice / buffers / combines, both grouped GEMMs on moe_qgemm or moe_q4gemm."""
+    from .quant import Mxfp4Experts
+
+    mx = isinstance(w13, Mxfp4Experts)
+    gemm = torch.ops.akap.moe_q4gemm if mx else torch.ops.akap.moe_qgemm
+    ring = _moe_qpf  # both kernels: 128-deep steps, ring depths 1 | 2 | 4
     T, d = h.shape
     K = topk_ids.shape[1]
     E = w13.shape[0]
@@ -810,25 +817,23 @@ def _fused_moe_fp8(h, w13, w2, topk_w, topk_ids, out):
     tile_expert = torch.empty(tiles, dtype=torch.int32, device=dev)
     sorted_ids, _, _ = moe_align(topk_ids, E, bm, inv=inv, tile_expert=tile_expert)
     act = torch.empty(cap, F, dtype=h.dtype, device=dev)
-    torch.ops.akap.moe_qgemm(act, h, w13.q, w13.scale, sorted_ids, tile_expert, n, K, True, True,
-                             _moe_qpf(d), bm)
+    gemm(act, h, w13.q, w13.scale, sorted_ids, tile_expert, n, K, True, True, ring(d), bm)
     S = moe_down_splitk(n, E, bm, F)
     if S > 1:
         P = torch.empty(S * cap * d, dtype=torch.float32, device=dev)
-        torch.ops.akap.moe_qgemm(P, act, w2.q, w2.scale, sorted_ids, tile_expert, n, K, False,
-                                 False, _moe_qpf(F // S), bm, S)
+        gemm(P, act, w2.q, w2.scale, sorted_ids, tile_expert, n, K, False, False, ring(F // S),
+             bm, S)
         torch.ops.akap.moe_combine_split(P, topk_w.contiguous(), inv, out, S, cap)
         return out
     y2 = torch.empty(cap, d, dtype=h.dtype, device=dev)
-    torch.ops.akap.moe_qgemm(y2, act, w2.q, w2.scale, sorted_ids, tile_expert, n, K, False, False,
-                             _moe_qpf(F), bm)
+    gemm(y2, act, w2.q, w2.scale, sorted_ids, tile_expert, n, K, False, False, ring(F), bm)
     torch.ops.akap.moe_combine(y2, topk_w.contiguous(), inv, out)
     return out
 
 
 def _moe_qpf(K: int) -> int:
-    """Deepest load ring of moe_qgemm (128-deep steps, the last maybe half) the reduction
-    depth allows."""
+    """Deepest load ring of moe_qgemm / moe_q4gemm (128-deep steps, the last maybe half) the
+    reduction depth allows."""
     if K % 64:
         raise ValueError(f"MoE GEMM needs K % 64 == 0, got {K}")
     steps = (K + 127) // 128

@@ -24,7 +24,7 @@ from typing import Optional, Sequence
 import torch
 
 from .gemm_variant import Variant
-from .quant import Fp8Experts, dequant_fp8_experts
+from .quant import QuantExperts, dequant_experts
 
 Choice = tuple  # ("torch",) | ("wgemm",) | ("hip", splitk) | ("dgemm", Variant)
 _PLAN: dict = {}
@@ -499,10 +499,10 @@ def tune_prefill(model, M: int, log=print, margin: float = 0.02) -> dict:
                                 generator=g).bincount(minlength=E)
         offs = cnt.cumsum(0).to(torch.int32).to(moe.w13.device)
         for w, silu in ((moe.w13, True), (moe.w2, False)):
-            if isinstance(w, Fp8Experts):
+            if isinstance(w, QuantExperts):
                 # the prefill path runs these GEMMs on the dequantized bf16 view (shared
                 # scratch): which grouped GEMM wins does not depend on where the bf16 came from
-                w = dequant_fp8_experts(w)
+                w = dequant_experts(w)
             _, N, K = w.shape
             if not pgemm_supported(rows, N, K):
                 continue

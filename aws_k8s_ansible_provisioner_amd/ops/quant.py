@@ -23,6 +23,10 @@ along K.
 accumulated in fp32.  An e2m1 value times such a power of two is exact in bf16, so the GPU
 kernel (csrc/kernels/q4gemm.hip) streams half-byte weights and widens them, block scale
 included, in registers.
+
+``Mxfp4Experts(q, scale)`` is the same for the experts of an MoE layer: ``q`` uint8
+[E, N, K/2], ``scale`` uint8 [E, N, K/32]; expert e follows the contract above with q[e] and
+scale[e] (the grouped kernel is csrc/kernels/moe_q4gemm.hip, which needs K % 128 == 0).
 """
 from __future__ import annotations
 
@@ -343,6 +347,149 @@ def quantize_mxfp4(w: torch.Tensor) -> Mxfp4Weight:
     c = torch.bucketize(r, grid)
     c = torch.where((w32 < 0) & (c > 0), c + 8, c).to(torch.uint8).reshape(N, K)
     return Mxfp4Weight(c[:, 0::2] | (c[:, 1::2] << 4), code.to(torch.uint8), check=False)
+
+
+class Mxfp4Experts:
+    """The MXFP4 weights of a group of MoE experts, [E, N, K]: ``q`` uint8 [E, N, K/2] (two e2m1
+    codes per byte, element 2j in the low nibble: Mxfp4Weight's packing), ``scale`` uint8
+    [E, N, K/32] of e8m0 codes in 2..252.  Per expert e
+
+        Y[r, n] = bf16(sum_k float(X[r, k]) * e2m1(q[e, n, k]) * 2^(scale[e, n, k/32] - 127))
+
+    accumulated in fp32 (csrc/kernels/moe_q4gemm.hip).  ``w[e]`` is expert e's Mxfp4Weight, so
+    code written for a bf16 [E, N, K] tensor that reads ``w[e].float()`` works unchanged."""
+
+    __slots__ = ("q", "scale")
+
+    def __init__(self, q: torch.Tensor, scale: torch.Tensor, check: bool = True):
+        fp4 = getattr(torch, "float4_e2m1fn_x2", None)
+        if fp4 is not None and q.dtype == fp4:
+            q = q.view(torch.uint8)
+        e8m0 = getattr(torch, "float8_e8m0fnu", None)
+        if e8m0 is not None and scale.dtype == e8m0:
+            scale = scale.view(torch.uint8)
+        if q.dtype != torch.uint8 or q.dim() != 3:
+            raise ValueError("Mxfp4Experts: q must be a 3-D uint8 tensor [E, N, K/2]")
+        if q.shape[2] % (MX_BLOCK // 2):
+            raise ValueError(f"Mxfp4Experts: K = {2 * q.shape[2]} must be a multiple of {MX_BLOCK}")
+        if (scale.dtype != torch.uint8 or scale.dim() != 3
+                or tuple(scale.shape) != (q.shape[0], q.shape[1], q.shape[2] // (MX_BLOCK // 2))):
+            raise ValueError("Mxfp4Experts: scale must be uint8 [E, N, K/32] (e8m0 codes)")
+        # check=False: slices and copies of a weight that was checked when it was built
+        if check and scale.numel() and bool(((scale < MX_SCALE_MIN) | (scale > MX_SCALE_MAX)).any()):
+            raise ValueError(f"Mxfp4Experts: e8m0 scale codes must lie in [{MX_SCALE_MIN}, "
+                             f"{MX_SCALE_MAX}] (255 is NaN; outside, a dequantized value is not "
+                             f"a normal bf16 number)")
+        self.q = q.contiguous()
+        self.scale = scale.contiguous()
+
+    @property
+    def shape(self) -> torch.Size:
+        return torch.Size((self.q.shape[0], self.q.shape[1], 2 * self.q.shape[2]))
+
+    @property
+    def device(self) -> torch.device:
+        return self.q.device
+
+    @property
+    def is_cuda(self) -> bool:
+        return self.q.is_cuda
+
+    @property
+    def dtype(self) -> torch.dtype:
+        return getattr(torch, "float4_e2m1fn_x2", torch.uint8)
+
+    def dim(self) -> int:
+        return 3
+
+    def numel(self) -> int:
+        return 2 * self.q.numel()
+
+    @property
+    def nbytes(self) -> int:
+        """E * N * K / 2 code bytes + E * N * K / 32 scale bytes."""
+        return self.q.numel() + self.scale.numel()
+
+    def flat(self) -> Mxfp4Weight:
+        """All experts' channels as one [E * N, K] Mxfp4Weight (a view: the dequantizer's
+        input)."""
+        E, N, K2 = self.q.shape
+        return Mxfp4Weight(self.q.view(E * N, K2), self.scale.view(E * N, -1), check=False)
+
+    def float(self) -> torch.Tensor:
+        """The dequantized fp32 tensor e2m1(q) * 2^(scale - 127) (exact)."""
+        return self.flat().float().view(self.shape)
+
+    def __getitem__(self, idx):
+        """w[e] -> expert e's Mxfp4Weight; w[a:b] -> the experts a..b (expert parallelism);
+        w[:, :, a:b] / w[:, a:b] -> column / channel slices of every expert (tensor
+        parallelism; column bounds must be multiples of 32, whole scale blocks)."""
+        idx = idx if isinstance(idx, tuple) else (idx,)
+        if len(idx) > 3:
+            raise IndexError("Mxfp4Experts: at most 3 indices")
+        ex, rows, cols = tuple(idx) + (slice(None),) * (3 - len(idx))
+        if not (isinstance(rows, slice) and isinstance(cols, slice)):
+            raise TypeError("Mxfp4Experts supports channel and column slices only")
+        a, b, step = cols.indices(self.shape[2])
+        if step != 1 or a % MX_BLOCK or b % MX_BLOCK:
+            raise ValueError(f"Mxfp4Experts: column slice [{a}:{b}] must start and end on "
+                             f"multiples of {MX_BLOCK}")
+        qc, sc = slice(a // 2, b // 2), slice(a // MX_BLOCK, b // MX_BLOCK)
+        if isinstance(ex, int):
+            return Mxfp4Weight(self.q[ex, rows, qc], self.scale[ex, rows, sc], check=False)
+        if not isinstance(ex, slice):
+            raise TypeError("Mxfp4Experts: the expert index is an int or a slice")
+        return Mxfp4Experts(self.q[ex, rows, qc], self.scale[ex, rows, sc], check=False)
+
+    def to(self, device) -> "Mxfp4Experts":
+        return Mxfp4Experts(self.q.to(device), self.scale.to(device), check=False)
+
+    def __repr__(self) -> str:
+        return f"Mxfp4Experts(shape={tuple(self.shape)}, device={self.device})"
+
+
+# what ops.fused_moe, MoEBlock and the byte accounting test an expert weight against
+QuantExperts = (Fp8Experts, Mxfp4Experts)
+
+
+@torch.no_grad()
+def quantize_mxfp4_experts(w: torch.Tensor) -> Mxfp4Experts:
+    """quantize_mxfp4's rule per expert of w [E, N, K]."""
+    if w.dim() != 3 or w.shape[2] % MX_BLOCK:
+        raise ValueError(f"quantize_mxfp4_experts: 3-D weight [E, N, K], K a multiple of {MX_BLOCK}")
+    E, N, K = w.shape
+    q = torch.empty(E, N, K // 2, dtype=torch.uint8, device=w.device)
+    scale = torch.empty(E, N, K // MX_BLOCK, dtype=torch.uint8, device=w.device)
+    for e in range(E):  # one expert's fp32 temporaries at a time
+        f = quantize_mxfp4(w[e])
+        q[e].copy_(f.q)
+        scale[e].copy_(f.scale)
+    return Mxfp4Experts(q, scale, check=False)
+
+
+def dequant_mxfp4_experts(w: Mxfp4Experts) -> torch.Tensor:
+    """bf16(e2m1(q) * 2^(scale - 127)) of all experts as a [E, N, K] view of the shared scratch
+    (GPU: the dequant_mxfp4 kernel, bit-exact; stream-ordered like every other use of the
+    scratch, never inside a captured region) or a new tensor (CPU)."""
+    if not w.is_cuda:
+        return w.float().to(torch.bfloat16)
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("mxfp4 experts are not dequantized inside a captured region")
+    from . import load_native
+
+    load_native(required=True)
+    f = w.flat()
+    reserve_scratch(f.numel(), f.device)
+    out = _scratch[f.device][: f.numel()].view(f.shape)
+    torch.ops.akap.dequant_mxfp4(out, f.q, f.scale)
+    return out.view(w.shape)
+
+
+def dequant_experts(w) -> torch.Tensor:
+    """dequant_fp8_experts / dequant_mxfp4_experts by container."""
+    if isinstance(w, Mxfp4Experts):
+        return dequant_mxfp4_experts(w)
+    return dequant_fp8_experts(w)
 
 
 # ------------------------------------------------------------------ dequantization scratch

@@ -641,10 +641,11 @@ def make_parser() -> argparse.ArgumentParser:
                          "mxfp4: e2m1 weights with one e8m0 scale per 32 elements along K, same "
                          "scope (loads uint8 weight + weight_scale checkpoints). "
                          "Default: AKAP_QUANTIZATION, else none")
-    ap.add_argument("--expert-quantization", default=None, choices=["none", "fp8"],
-                    help="MoE models: fp8 = per-(expert, channel) e4m3 expert weights, everything "
-                         "else bf16 (loads FP8 expert checkpoints, quantizes bf16 experts at "
-                         "start-up); --quantization stays none on an MoE model. "
+    ap.add_argument("--expert-quantization", default=None, choices=["none", "fp8", "mxfp4"],
+                    help="MoE models: fp8 = per-(expert, channel) e4m3 expert weights, mxfp4 = "
+                         "e2m1 expert weights with one e8m0 scale per 32 elements along K; "
+                         "everything else bf16 (loads expert checkpoints of that kind, quantizes "
+                         "bf16 experts at start-up); --quantization stays none on an MoE model. "
                          "Default: AKAP_EXPERT_QUANTIZATION, else none")
     ap.add_argument("--otlp-traces-endpoint", default=None,
                     help="OTLP/HTTP collector (e.g. http://otel-collector:4318); also read "
