@@ -1,6 +1,7 @@
 // Device helpers shared by the GEMM kernels (gemm / dgemm / gdgemm / kgemm / wgemm / qgemm /
-// pgemm / moe_dgemm / moe_qgemm / moe_q4gemm): LDS swizzle and LDS-DMA staging, counted waits, the epilogue arithmetic
-// whose rounding order is a contract with the CPU reference, and the split-K ticket step.
+// q4gemm / pgemm, and through moe_gemm_common.h moe_dgemm / moe_qgemm / moe_q4gemm): LDS swizzle
+// and LDS-DMA staging, counted waits, the epilogue arithmetic whose rounding order is a contract
+// with the CPU reference, and the split-K ticket step.
 #pragma once
 
 #include "common.h"
@@ -52,14 +53,9 @@ __device__ __forceinline__ bf16x8 fp4x8_to_bf16x8(uint32_t v, float scale) {
 // e8m0 code (2..252) -> 2^(code - 127)
 __device__ __forceinline__ float e8m0_to_f32(uint32_t code) { return __uint_as_float(code << 23); }
 
-// ---- per-channel scaled (FP8-weight) epilogues: moe_qgemm.hip ---------------------------------
-// The rounding order, a contract with the CPU reference (ops/quant.py): the scale of the weight
-// row multiplies the fp32 accumulator BEFORE the first rounding.
-//   store   y    = bf16(scale[e, n] * acc)
-//   SILU    g    = bf16(s_gate * acc_gate),  u = bf16(s_up * acc_up),  y = bf16(silu_bf(g) * u)
-//           with s_gate / s_up the scales of the weight rows the gate/up interleave read
-//   split   P[z] = scale[e, n] * acc_z   (fp32; moe_combine_split sums the slices)
-// qgemm.hip's store epilogue follows the same rule with scale[n].
+// ---- per-channel scaled (FP8-weight) epilogues ----------------------------------------------
+// The rounding order of moe_qgemm.hip's and qgemm.hip's scaled epilogues stands next to the
+// grouped kernels' tile epilogue in moe_gemm_common.h.
 
 // ---- EPI_RESNORM arithmetic -----------------------------------------------------------------
 // The fused residual / next-norm rounding order, a contract with the CPU reference and

@@ -185,37 +185,37 @@ inline bool q4gemm_supported(int M, int N, int K, int ldx, int ldy) {
          ldx % 8 == 0 && ldy % 8 == 0;
 }
 
-// ---- moe_dgemm.hip / moe.hip ----
-inline bool moe_dgemm_supported(int N, int K, int pf, int silu, int splitk) {
+// ---- moe_dgemm.hip / moe_qgemm.hip / moe_q4gemm.hip (moe_gemm_common.h) ----
+// What the three grouped kernels agree on: the compiled ring depths, K split evenly, no SILU
+// epilogue on fp32 partials, whole gate/up interleave groups (SILU) or 16-byte output rows.
+// Each adds its own depth rule.  N > 0 and K > 0 are not part of it: the bf16 predicate has
+// never tested them (an empty launch is a no-op there).
+inline bool moe_gemm_common_supported(int N, int K, int pf, int silu, int splitk) {
   if (pf != 1 && pf != 2 && pf != 4) return false;
-  if (splitk < 1 || K % splitk || (K / splitk) % (MBK * pf)) return false;
+  if (splitk < 1 || K % splitk) return false;
   if (silu && splitk > 1) return false;
   return silu ? N % 32 == 0 : N % 8 == 0;
 }
 
-// ---- moe_qgemm.hip: the FP8-expert form; a ring step is MQBK deep, and a slice whose depth is
-// an odd multiple of MBK ends in a half step, so pf = 1 takes every (N, K, silu, splitk) that
-// moe_dgemm_supported takes for some pf ----
+// bf16 weights: a ring step is MBK deep and a slice is whole ring turns
+inline bool moe_dgemm_supported(int N, int K, int pf, int silu, int splitk) {
+  return moe_gemm_common_supported(N, K, pf, silu, splitk) && (K / splitk) % (MBK * pf) == 0;
+}
+
+// FP8 weights: a ring step is MQBK deep, and a slice whose depth is an odd multiple of MBK ends
+// in a half step, so pf = 1 takes every (N, K, silu, splitk) that moe_dgemm_supported takes
+// for some pf
 constexpr int MQBK = 128;
 inline bool moe_qgemm_supported(int N, int K, int pf, int silu, int splitk) {
-  if (pf != 1 && pf != 2 && pf != 4) return false;
-  if (N <= 0 || K <= 0 || splitk < 1 || K % splitk || (K / splitk) % MBK) return false;
-  if (((K / splitk + MQBK - 1) / MQBK) % pf) return false;
-  if (silu && splitk > 1) return false;
-  return silu ? N % 32 == 0 : N % 8 == 0;
+  if (N <= 0 || K <= 0 || !moe_gemm_common_supported(N, K, pf, silu, splitk)) return false;
+  return (K / splitk) % MBK == 0 && ((K / splitk + MQBK - 1) / MQBK) % pf == 0;
 }
 
-// ---- moe_q4gemm.hip: the MXFP4-expert form; moe_qgemm's MQBK-deep ring step and half step.
-// A scale row is K / 32 bytes and a step reads 4 of them (a half step 2), so K % MQBK == 0;
-// with that, pf = 1 takes every (N, K, silu, splitk) that moe_dgemm_supported takes for some
-// pf ----
+// MXFP4 weights: moe_qgemm's ring step and half step.  A scale row is K / 32 bytes and a step
+// reads 4 of them (a half step 2), so K % MQBK == 0; with that, pf = 1 takes every (N, K, silu,
+// splitk) that moe_dgemm_supported takes for some pf
 inline bool moe_q4gemm_supported(int N, int K, int pf, int silu, int splitk) {
-  if (pf != 1 && pf != 2 && pf != 4) return false;
-  if (N <= 0 || K <= 0 || K % MQBK) return false;
-  if (splitk < 1 || K % splitk || (K / splitk) % MBK) return false;
-  if (((K / splitk + MQBK - 1) / MQBK) % pf) return false;
-  if (silu && splitk > 1) return false;
-  return silu ? N % 32 == 0 : N % 8 == 0;
+  return K % MQBK == 0 && moe_qgemm_supported(N, K, pf, silu, splitk);
 }
 
 inline bool moe_router_topk_supported(int E, int d) {

@@ -239,7 +239,7 @@ void launch_moe_combine_split(const float* P, const float* wts, const int32_t* i
 // ---- moe_qgemm.hip ----
 // The same grouped GEMM over FP8 expert weights: Wq uint8 [E, N, K] (OCP e4m3fn codes), scale
 // fp32 [E, N]; the scale multiplies the fp32 accumulator before the first rounding
-// (gemm_common.h).  No workspace, no cross-workgroup state.
+// (moe_gemm_common.h).  No workspace, no cross-workgroup state.
 void launch_moe_qgemm(const void* A, const void* Wq, const float* scale, void* Y,
                       const int32_t* sorted_ids, const int32_t* tile_expert, int max_tiles,
                       int n_flat, int topk, int N, int K, int lda, int ldy, int gather, int silu,

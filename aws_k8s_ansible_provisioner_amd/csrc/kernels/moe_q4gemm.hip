@@ -39,11 +39,9 @@
 //     operands are chunks 4 (fg & 1) + c of k-tile fg >> 1.  A and B agree on the order.
 //   * the block scale is applied at the widening (v_cvt_scalef32_pk_bf16_fp4, exact): there is
 //     no per-channel scale and no accumulator multiply; the epilogues are moe_dgemm.hip's.
-#include "gemm_common.h"
+#include "moe_gemm_common.h"
 
 namespace akap {
-
-constexpr int Q4MBN = 128;  // tile columns
 
 template <int BM, bool GATHER, bool SILU, int PF, bool SPLIT, bool NTW = false>
 __global__ __launch_bounds__(256, 2) void moe_q4gemm_kernel(const bf16* __restrict__ A,
@@ -55,17 +53,17 @@ __global__ __launch_bounds__(256, 2) void moe_q4gemm_kernel(const bf16* __restri
                                                             const int32_t* __restrict__ tile_expert,
                                                             int n_flat, int topk, int N, int K,
                                                             int lda, int ldy, int rows) {
-  constexpr int WM = BM / 32, WN = 4 / WM, WCOLS = Q4MBN / WN, JN = WCOLS / 16;
-  constexpr int AR = BM / 32;  // A rows staged per thread and k-tile
+  using T = MoeTile<BM>;
+  constexpr int WN = T::WN, WCOLS = T::WCOLS, JN = T::JN, AR = T::AR;  // AR: per k-tile
   // one __shared__ object, in 16-B units: [buf 2][A k-tile 0: BM rows x 8 | A k-tile 1: BM rows
   // x 8 | W: 128 rows x 4 | scale: 128 rows x 4 B = 32]
-  constexpr int WOFF = 2 * BM * 8, SOFF = WOFF + Q4MBN * 4;
-  constexpr int BUF = SOFF + Q4MBN / 4;
+  constexpr int WOFF = 2 * BM * 8, SOFF = WOFF + MOE_BN * 4;
+  constexpr int BUF = SOFF + MOE_BN / 4;
   __shared__ u32x4 lds[2 * BUF];
   const int tile = blockIdx.x;
   const int e = tile_expert[tile];
   if (e < 0) return;  // past the padded row count (graph-safe fixed grid); uniform exit
-  const int m0 = tile * BM, n0 = blockIdx.y * Q4MBN;
+  const int m0 = tile * BM, n0 = blockIdx.y * MOE_BN;
   // host: K % 128 == 0, kps % 64 == 0 and ceil(kps / 128) % PF == 0
   const int kps = K / gridDim.z, kbeg = blockIdx.z * kps, kend = kbeg + kps;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -75,26 +73,15 @@ __global__ __launch_bounds__(256, 2) void moe_q4gemm_kernel(const bf16* __restri
   const int w_ch = tid & 3, w_r = tid >> 2;    // W staging chunk / row (0..63)
   const int c_h = tid & 1, c_r = tid >> 1;     // scale staging pair / row (0..127)
 
-  // the weight row a virtual tile column reads (SILU: gate / up interleaved by 16)
-  auto wrow_of = [&](int v) {
-    if constexpr (SILU) return v < N ? ((v >> 4) & 1) * (N >> 1) + (v >> 5) * 16 + (v & 15) : 0;
-    return v < N ? v : 0;
-  };
   const bf16* xa[AR];
 #pragma unroll
-  for (int c = 0; c < AR; ++c) {
-    int arow = m0 + s_r + 32 * c;
-    if constexpr (GATHER) {
-      const int sid = sorted_ids[arow];
-      arow = sid < n_flat ? sid / topk : 0;
-    }
-    xa[c] = A + (size_t)arow * lda;
-  }
+  for (int c = 0; c < AR; ++c)
+    xa[c] = moe_a_row<GATHER>(A, sorted_ids, m0 + s_r + 32 * c, n_flat, topk, lda);
   const uint8_t* wb[2];
 #pragma unroll
   for (int c = 0; c < 2; ++c)
-    wb[c] = W + ((size_t)e * N + wrow_of(n0 + w_r + 64 * c)) * (K >> 1) + w_ch * 16;
-  const uint8_t* cb = scale + ((size_t)e * N + wrow_of(n0 + c_r)) * (K >> 5) + c_h * 2;
+    wb[c] = W + ((size_t)e * N + moe_wrow<SILU>(n0 + w_r + 64 * c, N)) * (K >> 1) + w_ch * 16;
+  const uint8_t* cb = scale + ((size_t)e * N + moe_wrow<SILU>(n0 + c_r, N)) * (K >> 5) + c_h * 2;
 
   u32x4 sa[PF][2][AR], sb[PF][2];
   uint32_t sc[PF];
@@ -118,11 +105,7 @@ __global__ __launch_bounds__(256, 2) void moe_q4gemm_kernel(const bf16* __restri
     if (full || c_h == 0) sc[q] = *reinterpret_cast<const uint16_t*>(cb + (k0 >> 5));
   };
   auto sstore = [&](int q, int buf) {
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-      for (int c = 0; c < AR; ++c)
-        lds[buf * BUF + h * BM * 8 + swz8(s_r + 32 * c, s_ch)] = sa[q][h][c];
+    moe_sstore_a2<BM>(&lds[buf * BUF], sa[q], s_r, s_ch);
 #pragma unroll
     for (int c = 0; c < 2; ++c) lds[buf * BUF + WOFF + q4swz_w(w_r + 64 * c, w_ch)] = sb[q][c];
     reinterpret_cast<uint16_t*>(&lds[buf * BUF + SOFF])[tid] = (uint16_t)sc[q];
@@ -132,7 +115,7 @@ __global__ __launch_bounds__(256, 2) void moe_q4gemm_kernel(const bf16* __restri
   for (int i = 0; i < 2; ++i)
 #pragma unroll
     for (int j = 0; j < JN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  auto mfma = [&](int buf) {
+  auto mfma = [&](int buf, bool) {
     const u32x4* xh = &lds[buf * BUF + (fg >> 1) * BM * 8];  // this lane group's k-tile
     const uint32_t* sw = reinterpret_cast<const uint32_t*>(&lds[buf * BUF + SOFF]);
     bf16x8 a[4][2];
@@ -157,112 +140,24 @@ __global__ __launch_bounds__(256, 2) void moe_q4gemm_kernel(const bf16* __restri
   };
 
   const int nk = (kps + 127) / 128;  // steps of this slice, the last maybe half
-#pragma unroll
-  for (int q = 0; q < PF; ++q) gload(q, kbeg + q * 128);
-  int t = 0;
-  for (; t + PF < nk; t += PF) {
-#pragma unroll
-    for (int q = 0; q < PF; ++q) {
-      const int buf = (t + q) & 1;
-      sstore(q, buf);
-      __syncthreads();
-      gload(q, kbeg + (t + q + PF) * 128);
-      __builtin_amdgcn_sched_barrier(0);  // keep the refill here (see dgemm.hip)
-      mfma(buf);
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < PF; ++q) {
-    const int buf = (t + q) & 1;
-    sstore(q, buf);
-    __syncthreads();
-    mfma(buf);
-  }
-
-  // epilogue (moe_dgemm.hip's): lane holds rows wm*32 + i*16 + fg*4 + r, column fr of each
-  // 16-col sub-tile j
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = m0 + wm * 32 + i * 16 + fg * 4 + r;
-      if constexpr (SILU) {
-#pragma unroll
-        for (int jj = 0; jj < JN / 2; ++jj) {  // sub-tiles 2jj / 2jj+1 = gate / up
-          const int vb = n0 + wn * WCOLS + 32 * jj;
-          if (vb + 16 + fr < N) {
-            const float g = bf2f(f2bf(acc[i][2 * jj][r]));
-            const float u = bf2f(f2bf(acc[i][2 * jj + 1][r]));
-            Y[(size_t)row * ldy + (vb >> 1) + fr] = f2bf(silu_bf(g) * u);
-          }
-        }
-      } else if constexpr (SPLIT) {
-        float* pz = P + ((size_t)blockIdx.z * rows + row) * N;
-#pragma unroll
-        for (int j = 0; j < JN; ++j) {
-          const int col = n0 + wn * WCOLS + j * 16 + fr;
-          if (col < N) pz[col] = acc[i][j][r];
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < JN; ++j) {
-          const int col = n0 + wn * WCOLS + j * 16 + fr;
-          if (col < N) Y[(size_t)row * ldy + col] = f2bf(acc[i][j][r]);
-        }
-      }
-    }
+  MOE_RING(PF, 128, nk, kbeg, gload, sstore, mfma);
+  MOE_TILE_EPILOGUE(MOE_NO_SCALE)
 }
 
-template <int BM, bool G, bool S, bool SPL>
-static void moe_q4gemm_pf(dim3 grid, int pf, bool ntw, hipStream_t s, const bf16* A,
-                          const uint8_t* W, const uint8_t* scale, bf16* Y, float* P,
-                          const int32_t* sid, const int32_t* te, int n_flat, int topk, int N,
-                          int K, int lda, int ldy, int rows) {
-#define MOEQ4_L(PFV, NT) moe_q4gemm_kernel<BM, G, S, PFV, SPL, NT><<<grid, 256, 0, s>>>( \
-      A, W, scale, Y, P, sid, te, n_flat, topk, N, K, lda, ldy, rows)
-  switch (pf) {
-    case 4: if (ntw) MOEQ4_L(4, true); else MOEQ4_L(4, false); break;
-    case 2: if (ntw) MOEQ4_L(2, true); else MOEQ4_L(2, false); break;
-    default: MOEQ4_L(1, false);
+struct MoeQ4gemmFamily {
+  template <int BM, bool G, bool S, int PF, bool SPL, bool NT, typename... Args>
+  static void launch(dim3 grid, hipStream_t s, Args... a) {
+    moe_q4gemm_kernel<BM, G, S, PF, SPL, NT><<<grid, 256, 0, s>>>(a...);
   }
-#undef MOEQ4_L
-}
-
-template <int BM>
-static void moe_q4gemm_bm(dim3 grid, int gather, int silu, int pf, bool ntw, hipStream_t s,
-                          const bf16* a, const uint8_t* w, const uint8_t* sc, bf16* y, float* P,
-                          const int32_t* sid, const int32_t* te, int n_flat, int topk, int N,
-                          int K, int lda, int ldy, int rows) {
-  const bool spl = grid.z > 1;
-  if (gather && silu)
-    moe_q4gemm_pf<BM, true, true, false>(grid, pf, ntw, s, a, w, sc, y, P, sid, te, n_flat, topk, N, K, lda, ldy, rows);
-  else if (silu)
-    moe_q4gemm_pf<BM, false, true, false>(grid, pf, ntw, s, a, w, sc, y, P, sid, te, n_flat, topk, N, K, lda, ldy, rows);
-  else if (gather && spl)
-    moe_q4gemm_pf<BM, true, false, true>(grid, pf, ntw, s, a, w, sc, y, P, sid, te, n_flat, topk, N, K, lda, ldy, rows);
-  else if (gather)
-    moe_q4gemm_pf<BM, true, false, false>(grid, pf, ntw, s, a, w, sc, y, P, sid, te, n_flat, topk, N, K, lda, ldy, rows);
-  else if (spl)
-    moe_q4gemm_pf<BM, false, false, true>(grid, pf, ntw, s, a, w, sc, y, P, sid, te, n_flat, topk, N, K, lda, ldy, rows);
-  else
-    moe_q4gemm_pf<BM, false, false, false>(grid, pf, ntw, s, a, w, sc, y, P, sid, te, n_flat, topk, N, K, lda, ldy, rows);
-}
+};
 
 void launch_moe_q4gemm(const void* A, const void* Wq, const void* scale, void* Y,
                        const int32_t* sorted_ids, const int32_t* tile_expert, int max_tiles,
                        int n_flat, int topk, int N, int K, int lda, int ldy, int gather, int silu,
                        int pf, int bm, int splitk, float* partials, bool ntw, hipStream_t s) {
-  if (max_tiles == 0) return;
-  dim3 grid(max_tiles, (N + Q4MBN - 1) / Q4MBN, splitk);
-  const bf16* a = (const bf16*)A;
-  const uint8_t* w = (const uint8_t*)Wq;
-  const uint8_t* sc = (const uint8_t*)scale;
-  bf16* y = (bf16*)Y;
-  const int rows = max_tiles * bm;
-  if (bm == 64)
-    moe_q4gemm_bm<64>(grid, gather, silu, pf, ntw, s, a, w, sc, y, partials, sorted_ids, tile_expert, n_flat, topk, N, K, lda, ldy, rows);
-  else
-    moe_q4gemm_bm<32>(grid, gather, silu, pf, ntw, s, a, w, sc, y, partials, sorted_ids, tile_expert, n_flat, topk, N, K, lda, ldy, rows);
+  moe_launch<MoeQ4gemmFamily>(max_tiles, N, splitk, bm, gather, silu, pf, ntw, s, (const bf16*)A,
+                              (const uint8_t*)Wq, (const uint8_t*)scale, (bf16*)Y, partials,
+                              sorted_ids, tile_expert, n_flat, topk, N, K, lda, ldy);
 }
 
 }  // namespace akap

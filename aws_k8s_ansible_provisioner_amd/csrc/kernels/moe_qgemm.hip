@@ -29,12 +29,10 @@
 //   * fragment k-order: lane group fg of MFMA pair ks owns k in [64 ks + 16 fg, +16): ONE
 //     ds_read_b128 of the fp8 row feeds both MFMAs (low 8 bytes, high 8 bytes); the A
 //     operands are chunks 2 fg and 2 fg + 1 of k-tile ks.  A and B agree on the order.
-//   * the scale multiplies the fp32 accumulator before the first rounding (gemm_common.h).
-#include "gemm_common.h"
+//   * the scale multiplies the fp32 accumulator before the first rounding (moe_gemm_common.h).
+#include "moe_gemm_common.h"
 
 namespace akap {
-
-constexpr int QMBN = 128;  // tile columns
 
 template <int BM, bool GATHER, bool SILU, int PF, bool SPLIT, bool NTW = false>
 __global__ __launch_bounds__(256, 2) void moe_qgemm_kernel(const bf16* __restrict__ A,
@@ -46,16 +44,16 @@ __global__ __launch_bounds__(256, 2) void moe_qgemm_kernel(const bf16* __restric
                                                            const int32_t* __restrict__ tile_expert,
                                                            int n_flat, int topk, int N, int K,
                                                            int lda, int ldy, int rows) {
-  constexpr int WM = BM / 32, WN = 4 / WM, WCOLS = QMBN / WN, JN = WCOLS / 16;
-  constexpr int AR = BM / 32;  // A rows staged per thread and k-tile
+  using T = MoeTile<BM>;
+  constexpr int WN = T::WN, WCOLS = T::WCOLS, JN = T::JN, AR = T::AR;  // AR: per k-tile
   // one __shared__ object: [buf 2][A k-tile 0: BM rows | A k-tile 1: BM rows | W 128 rows]
   // [8 chunks of 16 B]
-  constexpr int BUF = (2 * BM + QMBN) * 8;
+  constexpr int BUF = (2 * BM + MOE_BN) * 8;
   __shared__ u32x4 lds[2 * BUF];
   const int tile = blockIdx.x;
   const int e = tile_expert[tile];
   if (e < 0) return;  // past the padded row count (graph-safe fixed grid); uniform exit
-  const int m0 = tile * BM, n0 = blockIdx.y * QMBN;
+  const int m0 = tile * BM, n0 = blockIdx.y * MOE_BN;
   // host: kps % 64 == 0 and ceil(kps / 128) % PF == 0
   const int kps = K / gridDim.z, kbeg = blockIdx.z * kps, kend = kbeg + kps;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -65,20 +63,12 @@ __global__ __launch_bounds__(256, 2) void moe_qgemm_kernel(const bf16* __restric
 
   const bf16* xa[AR];
 #pragma unroll
-  for (int c = 0; c < AR; ++c) {
-    int arow = m0 + s_r + 32 * c;
-    if constexpr (GATHER) {
-      const int sid = sorted_ids[arow];
-      arow = sid < n_flat ? sid / topk : 0;
-    }
-    xa[c] = A + (size_t)arow * lda;
-  }
+  for (int c = 0; c < AR; ++c)
+    xa[c] = moe_a_row<GATHER>(A, sorted_ids, m0 + s_r + 32 * c, n_flat, topk, lda);
   const uint8_t* wb[4];
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
-    const int v = n0 + s_r + 32 * c;  // virtual column
-    int wrow = v < N ? v : 0;
-    if constexpr (SILU) wrow = v < N ? ((v >> 4) & 1) * (N >> 1) + (v >> 5) * 16 + (v & 15) : 0;
+    const int wrow = moe_wrow<SILU>(n0 + s_r + 32 * c, N);
     wb[c] = W + ((size_t)e * N + wrow) * K;
   }
 
@@ -101,11 +91,7 @@ __global__ __launch_bounds__(256, 2) void moe_qgemm_kernel(const bf16* __restric
     }
   };
   auto sstore = [&](int q, int buf) {
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-      for (int c = 0; c < AR; ++c)
-        lds[buf * BUF + h * BM * 8 + swz8(s_r + 32 * c, s_ch)] = sa[q][h][c];
+    moe_sstore_a2<BM>(&lds[buf * BUF], sa[q], s_r, s_ch);
 #pragma unroll
     for (int c = 0; c < 4; ++c) lds[buf * BUF + 2 * BM * 8 + swz8(s_r + 32 * c, s_ch)] = sb[q][c];
   };
@@ -115,7 +101,8 @@ __global__ __launch_bounds__(256, 2) void moe_qgemm_kernel(const bf16* __restric
 #pragma unroll
     for (int j = 0; j < JN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   // nks: k-tiles of the step to multiply (2, or 1 for the half step that ends a slice)
-  auto mfma = [&](int buf, int nks) {
+  auto mfma = [&](int buf, bool last) {
+    const int nks = last && (kps & 127) ? 1 : 2;
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       if (ks < nks) {
@@ -141,31 +128,9 @@ __global__ __launch_bounds__(256, 2) void moe_qgemm_kernel(const bf16* __restric
     }
   };
 
-  const int nk = (kps + 127) / 128;           // steps of this slice, the last maybe half
-  const int last_nks = (kps & 127) ? 1 : 2;   // k-tiles of the last step
-#pragma unroll
-  for (int q = 0; q < PF; ++q) gload(q, kbeg + q * 128);
-  int t = 0;
-  for (; t + PF < nk; t += PF) {
-#pragma unroll
-    for (int q = 0; q < PF; ++q) {
-      const int buf = (t + q) & 1;
-      sstore(q, buf);
-      __syncthreads();
-      gload(q, kbeg + (t + q + PF) * 128);
-      __builtin_amdgcn_sched_barrier(0);  // keep the refill here (see dgemm.hip)
-      mfma(buf, 2);
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < PF; ++q) {
-    const int buf = (t + q) & 1;
-    sstore(q, buf);
-    __syncthreads();
-    mfma(buf, q == PF - 1 ? last_nks : 2);
-  }
+  const int nk = (kps + 127) / 128;  // steps of this slice, the last maybe half
+  MOE_RING(PF, 128, nk, kbeg, gload, sstore, mfma);
 
-  // epilogue: lane holds rows wm*32 + i*16 + fg*4 + r, column fr of each 16-col sub-tile j.
   // sc[j]: the scale of the weight row sub-tile j's column fr was read from (SILU: the
   // interleave maps sub-tile 2jj to gate row vb/2 + fr and 2jj+1 to up row N/2 + vb/2 + fr)
   const float* se = scale + (size_t)e * N;
@@ -173,91 +138,27 @@ __global__ __launch_bounds__(256, 2) void moe_qgemm_kernel(const bf16* __restric
 #pragma unroll
   for (int j = 0; j < JN; ++j) {
     const int v = n0 + wn * WCOLS + j * 16 + fr;  // virtual column
-    int srow = v;
-    if constexpr (SILU) srow = ((v >> 4) & 1) * (N >> 1) + (v >> 5) * 16 + (v & 15);
-    sc[j] = v < N ? se[srow] : 0.f;
+    sc[j] = v < N ? se[moe_wrow<SILU>(v, N)] : 0.f;
   }
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = m0 + wm * 32 + i * 16 + fg * 4 + r;
-      if constexpr (SILU) {
-#pragma unroll
-        for (int jj = 0; jj < JN / 2; ++jj) {  // sub-tiles 2jj / 2jj+1 = gate / up
-          const int vb = n0 + wn * WCOLS + 32 * jj;
-          if (vb + 16 + fr < N) {
-            const float g = bf2f(f2bf(sc[2 * jj] * acc[i][2 * jj][r]));
-            const float u = bf2f(f2bf(sc[2 * jj + 1] * acc[i][2 * jj + 1][r]));
-            Y[(size_t)row * ldy + (vb >> 1) + fr] = f2bf(silu_bf(g) * u);
-          }
-        }
-      } else if constexpr (SPLIT) {
-        float* pz = P + ((size_t)blockIdx.z * rows + row) * N;
-#pragma unroll
-        for (int j = 0; j < JN; ++j) {
-          const int col = n0 + wn * WCOLS + j * 16 + fr;
-          if (col < N) pz[col] = sc[j] * acc[i][j][r];
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < JN; ++j) {
-          const int col = n0 + wn * WCOLS + j * 16 + fr;
-          if (col < N) Y[(size_t)row * ldy + col] = f2bf(sc[j] * acc[i][j][r]);
-        }
-      }
-    }
+#define MOEQ_SCALED(j, x) (sc[j] * (x))  // the scale before the first rounding
+  MOE_TILE_EPILOGUE(MOEQ_SCALED)
+#undef MOEQ_SCALED
 }
 
-template <int BM, bool G, bool S, bool SPL>
-static void moe_qgemm_pf(dim3 grid, int pf, bool ntw, hipStream_t s, const bf16* A,
-                         const uint8_t* W, const float* scale, bf16* Y, float* P,
-                         const int32_t* sid, const int32_t* te, int n_flat, int topk, int N,
-                         int K, int lda, int ldy, int rows) {
-#define MOEQ_L(PFV, NT) moe_qgemm_kernel<BM, G, S, PFV, SPL, NT><<<grid, 256, 0, s>>>( \
-      A, W, scale, Y, P, sid, te, n_flat, topk, N, K, lda, ldy, rows)
-  switch (pf) {
-    case 4: if (ntw) MOEQ_L(4, true); else MOEQ_L(4, false); break;
-    case 2: if (ntw) MOEQ_L(2, true); else MOEQ_L(2, false); break;
-    default: MOEQ_L(1, false);
+struct MoeQgemmFamily {
+  template <int BM, bool G, bool S, int PF, bool SPL, bool NT, typename... Args>
+  static void launch(dim3 grid, hipStream_t s, Args... a) {
+    moe_qgemm_kernel<BM, G, S, PF, SPL, NT><<<grid, 256, 0, s>>>(a...);
   }
-#undef MOEQ_L
-}
-
-template <int BM>
-static void moe_qgemm_bm(dim3 grid, int gather, int silu, int pf, bool ntw, hipStream_t s,
-                         const bf16* a, const uint8_t* w, const float* sc, bf16* y, float* P,
-                         const int32_t* sid, const int32_t* te, int n_flat, int topk, int N,
-                         int K, int lda, int ldy, int rows) {
-  const bool spl = grid.z > 1;
-  if (gather && silu)
-    moe_qgemm_pf<BM, true, true, false>(grid, pf, ntw, s, a, w, sc, y, P, sid, te, n_flat, topk, N, K, lda, ldy, rows);
-  else if (silu)
-    moe_qgemm_pf<BM, false, true, false>(grid, pf, ntw, s, a, w, sc, y, P, sid, te, n_flat, topk, N, K, lda, ldy, rows);
-  else if (gather && spl)
-    moe_qgemm_pf<BM, true, false, true>(grid, pf, ntw, s, a, w, sc, y, P, sid, te, n_flat, topk, N, K, lda, ldy, rows);
-  else if (gather)
-    moe_qgemm_pf<BM, true, false, false>(grid, pf, ntw, s, a, w, sc, y, P, sid, te, n_flat, topk, N, K, lda, ldy, rows);
-  else if (spl)
-    moe_qgemm_pf<BM, false, false, true>(grid, pf, ntw, s, a, w, sc, y, P, sid, te, n_flat, topk, N, K, lda, ldy, rows);
-  else
-    moe_qgemm_pf<BM, false, false, false>(grid, pf, ntw, s, a, w, sc, y, P, sid, te, n_flat, topk, N, K, lda, ldy, rows);
-}
+};
 
 void launch_moe_qgemm(const void* A, const void* Wq, const float* scale, void* Y,
                       const int32_t* sorted_ids, const int32_t* tile_expert, int max_tiles,
                       int n_flat, int topk, int N, int K, int lda, int ldy, int gather, int silu,
                       int pf, int bm, int splitk, float* partials, bool ntw, hipStream_t s) {
-  if (max_tiles == 0) return;
-  dim3 grid(max_tiles, (N + QMBN - 1) / QMBN, splitk);
-  const bf16* a = (const bf16*)A;
-  const uint8_t* w = (const uint8_t*)Wq;
-  bf16* y = (bf16*)Y;
-  const int rows = max_tiles * bm;
-  if (bm == 64)
-    moe_qgemm_bm<64>(grid, gather, silu, pf, ntw, s, a, w, scale, y, partials, sorted_ids, tile_expert, n_flat, topk, N, K, lda, ldy, rows);
-  else
-    moe_qgemm_bm<32>(grid, gather, silu, pf, ntw, s, a, w, scale, y, partials, sorted_ids, tile_expert, n_flat, topk, N, K, lda, ldy, rows);
+  moe_launch<MoeQgemmFamily>(max_tiles, N, splitk, bm, gather, silu, pf, ntw, s, (const bf16*)A,
+                             (const uint8_t*)Wq, scale, (bf16*)Y, partials, sorted_ids,
+                             tile_expert, n_flat, topk, N, K, lda, ldy);
 }
 
 }  // namespace akap

@@ -675,27 +675,41 @@ void moe_gemm(Tensor out, Tensor a, Tensor w, Tensor sorted_ids, Tensor tile_exp
                         a.stride(0), gather ? 1 : 0, cur_stream());
 }
 
+// What moe_dgemm / moe_qgemm / moe_q4gemm hand to their launchers besides the weights.
+struct MoeGemmArgs {
+  const void* a;
+  void* y;          // bf16 [rows, out width], or null with splitk > 1
+  float* partials;  // splitk > 1: fp32 [splitk, rows, N]
+  const int32_t* sorted_ids;
+  const int32_t* tile_expert;
+  int max_tiles, n_flat, topk, lda, ldy, gather, silu, pf, bm, splitk;
+  bool ntw;
+};
+
+// The checks and arguments the three grouped expert GEMMs share.  The caller has checked its
+// weight and scale shapes (E experts of [N, K]) and passes its *_supported predicate's answer.
 // out: bf16 [rows, N] (or [rows, N/2] with silu); splitk > 1: out is an fp32 partials buffer
 // [splitk, rows, N] consumed by moe_combine_split.
-void moe_dgemm(Tensor out, Tensor a, Tensor w, Tensor sorted_ids, Tensor tile_expert,
-               int64_t n_flat, int64_t topk, bool gather, bool silu, int64_t pf, int64_t bm,
-               int64_t splitk) {
-  const OpArgs o = on_gpu("moe_dgemm", a, "a");
-  TORCH_CHECK(w.dim() == 3 && a.dim() == 2, "moe_dgemm: a [rows, K], expert weights [E, N, K]");
-  const int N = w.size(1), K = w.size(2);
-  TORCH_CHECK(a.size(1) == K, "moe_dgemm: a width != K");
-  TORCH_CHECK(akap::moe_dgemm_supported(N, K, pf, silu, splitk), "moe_dgemm: unsupported N/K/pf/split");
-  TORCH_CHECK(a.stride(0) % 8 == 0, "moe_dgemm: 16-byte aligned rows");
-  TORCH_CHECK(bm == 32 || bm == 64, "moe_dgemm: tile rows 32 | 64");
-  const int max_tiles = tile_expert.numel();
-  const int64_t rows = (int64_t)max_tiles * bm;
-  // split-K: out is the fp32 partials [splitk, rows, N]
-  float* partials = splitk > 1 ? o.ptr<float>(out, "out", splitk * rows * N) : nullptr;
-  void* y = splitk > 1 ? nullptr : o.bf16(out, "out");
+static MoeGemmArgs moe_gemm_args(const OpArgs& o, const Tensor& out, const Tensor& a,
+                                 const Tensor& sorted_ids, const Tensor& tile_expert, int64_t E,
+                                 int N, int K, bool supported, int64_t n_flat, int64_t topk,
+                                 bool gather, bool silu, int64_t pf, int64_t bm, int64_t splitk) {
+  const char* op = o.op();
+  TORCH_CHECK(a.size(1) == K, op, ": a width != K");
+  TORCH_CHECK(supported, op, ": unsupported N/K/pf/split");
+  TORCH_CHECK(a.stride(0) % 8 == 0, op, ": 16-byte aligned rows");
+  TORCH_CHECK(bm == 32 || bm == 64, op, ": tile rows 32 | 64");
+  TORCH_CHECK(topk >= 1 && n_flat >= 0, op, ": topk >= 1, n_flat >= 0");
+  MoeGemmArgs g{};
+  g.max_tiles = tile_expert.numel();
+  const int64_t rows = (int64_t)g.max_tiles * bm;
+  g.partials = splitk > 1 ? o.ptr<float>(out, "out", splitk * rows * N) : nullptr;
+  g.y = splitk > 1 ? nullptr : o.bf16(out, "out");
   TORCH_CHECK(splitk > 1 || (out.dim() == 2 && out.size(1) == (silu ? N / 2 : N)),
-              "moe_dgemm: out width");
-  TORCH_CHECK(splitk > 1 || out.size(0) >= rows, "moe_dgemm: out rows must cover all tiles");
-  TORCH_CHECK(gather || a.size(0) >= rows, "moe_dgemm: a rows must cover all tiles");
+              op, ": out width");
+  TORCH_CHECK(splitk > 1 || out.size(0) >= rows, op, ": out rows must cover all tiles");
+  TORCH_CHECK(gather ? a.size(0) * topk >= n_flat : a.size(0) >= rows,
+              op, ": a rows must cover all tiles (gather: all n_flat / topk tokens)");
   // Non-temporal expert-weight loads when each expert's weights are streamed by one row tile
   // (64-row tiles, <= 40 rows per expert on average): measured on MI355X, Mixtral T=128,
   // w13 345 -> 319 us, w2 (split 4) 226 -> 215 us; with 32-row tiles an expert's second tile
@@ -705,13 +719,29 @@ void moe_dgemm(Tensor out, Tensor a, Tensor w, Tensor sorted_ids, Tensor tile_ex
     const char* e = std::getenv("AKAP_MOE_NT");
     return e ? std::atoi(e) : -1;
   }();
-  const bool ntw = nt_env >= 0 ? nt_env != 0 : (bm == 64 && n_flat <= 40 * w.size(0));
-  akap::launch_moe_dgemm(o.bf16(a, "a", 0, kLastContig), o.bf16(w, "w"), y,
-                         o.ptr<int32_t>(sorted_ids, "sorted_ids", rows),
-                         o.ptr<int32_t>(tile_expert, "tile_expert"), max_tiles, n_flat, topk, N,
-                         K, a.stride(0), splitk > 1 ? N : out.stride(0), gather ? 1 : 0,
-                         silu ? 1 : 0, (int)pf, (int)bm, (int)splitk, partials, ntw,
-                         cur_stream());
+  g.ntw = nt_env >= 0 ? nt_env != 0 : (bm == 64 && n_flat <= 40 * E);
+  g.a = o.bf16(a, "a", 0, kLastContig | kAlign16);
+  g.sorted_ids = o.ptr<int32_t>(sorted_ids, "sorted_ids", rows);
+  g.tile_expert = o.ptr<int32_t>(tile_expert, "tile_expert");
+  g.n_flat = n_flat; g.topk = topk;
+  g.lda = a.stride(0); g.ldy = splitk > 1 ? N : out.stride(0);
+  g.gather = gather ? 1 : 0; g.silu = silu ? 1 : 0;
+  g.pf = (int)pf; g.bm = (int)bm; g.splitk = (int)splitk;
+  return g;
+}
+
+void moe_dgemm(Tensor out, Tensor a, Tensor w, Tensor sorted_ids, Tensor tile_expert,
+               int64_t n_flat, int64_t topk, bool gather, bool silu, int64_t pf, int64_t bm,
+               int64_t splitk) {
+  const OpArgs o = on_gpu("moe_dgemm", a, "a");
+  TORCH_CHECK(w.dim() == 3 && a.dim() == 2, "moe_dgemm: a [rows, K], expert weights [E, N, K]");
+  const int N = w.size(1), K = w.size(2);
+  const MoeGemmArgs g = moe_gemm_args(o, out, a, sorted_ids, tile_expert, w.size(0), N, K,
+                                      akap::moe_dgemm_supported(N, K, pf, silu, splitk), n_flat,
+                                      topk, gather, silu, pf, bm, splitk);
+  akap::launch_moe_dgemm(g.a, o.bf16(w, "w"), g.y, g.sorted_ids, g.tile_expert, g.max_tiles,
+                         g.n_flat, g.topk, N, K, g.lda, g.ldy, g.gather, g.silu, g.pf, g.bm,
+                         g.splitk, g.partials, g.ntw, cur_stream());
 }
 
 // moe_dgemm over FP8 expert weights (csrc/kernels/moe_qgemm.hip): wq uint8 / float8_e4m3fn
@@ -726,36 +756,14 @@ void moe_qgemm(Tensor out, Tensor a, Tensor wq, Tensor scale, Tensor sorted_ids,
   const int N = wq.size(1), K = wq.size(2);
   TORCH_CHECK(scale.dim() == 2 && scale.size(0) == E && scale.size(1) == N,
               "moe_qgemm: scale must be [E, N]");
-  TORCH_CHECK(a.size(1) == K, "moe_qgemm: a width != K");
-  TORCH_CHECK(akap::moe_qgemm_supported(N, K, pf, silu, splitk),
-              "moe_qgemm: unsupported N/K/pf/split");
-  TORCH_CHECK(a.stride(0) % 8 == 0, "moe_qgemm: 16-byte aligned rows");
-  TORCH_CHECK(bm == 32 || bm == 64, "moe_qgemm: tile rows 32 | 64");
-  TORCH_CHECK(topk >= 1 && n_flat >= 0, "moe_qgemm: topk >= 1, n_flat >= 0");
-  const int max_tiles = tile_expert.numel();
-  const int64_t rows = (int64_t)max_tiles * bm;
-  // split-K: out is the fp32 partials [splitk, rows, N]
-  float* partials = splitk > 1 ? o.ptr<float>(out, "out", splitk * rows * N) : nullptr;
-  void* y = splitk > 1 ? nullptr : o.bf16(out, "out");
-  TORCH_CHECK(splitk > 1 || (out.dim() == 2 && out.size(1) == (silu ? N / 2 : N)),
-              "moe_qgemm: out width");
-  TORCH_CHECK(splitk > 1 || out.size(0) >= rows, "moe_qgemm: out rows must cover all tiles");
-  TORCH_CHECK(gather ? a.size(0) * topk >= n_flat : a.size(0) >= rows,
-              "moe_qgemm: a rows must cover all tiles (gather: all n_flat / topk tokens)");
-  // the non-temporal policy of moe_dgemm (one row tile per expert streams its weights once)
-  static const int nt_env = [] {
-    const char* e = std::getenv("AKAP_MOE_NT");
-    return e ? std::atoi(e) : -1;
-  }();
-  const bool ntw = nt_env >= 0 ? nt_env != 0 : (bm == 64 && n_flat <= 40 * E);
-  akap::launch_moe_qgemm(o.bf16(a, "a", 0, kLastContig | kAlign16),
+  const MoeGemmArgs g = moe_gemm_args(o, out, a, sorted_ids, tile_expert, E, N, K,
+                                      akap::moe_qgemm_supported(N, K, pf, silu, splitk), n_flat,
+                                      topk, gather, silu, pf, bm, splitk);
+  akap::launch_moe_qgemm(g.a,
                          o.ptr(wq, "wq", {at::kByte, at::kFloat8_e4m3fn}, 0, kContig | kAlign16),
-                         o.ptr<float>(scale, "scale", E * N), y,
-                         o.ptr<int32_t>(sorted_ids, "sorted_ids", rows),
-                         o.ptr<int32_t>(tile_expert, "tile_expert"), max_tiles, n_flat, topk, N,
-                         K, a.stride(0), splitk > 1 ? N : out.stride(0), gather ? 1 : 0,
-                         silu ? 1 : 0, (int)pf, (int)bm, (int)splitk, partials, ntw,
-                         cur_stream());
+                         o.ptr<float>(scale, "scale", E * N), g.y, g.sorted_ids, g.tile_expert,
+                         g.max_tiles, g.n_flat, g.topk, N, K, g.lda, g.ldy, g.gather, g.silu,
+                         g.pf, g.bm, g.splitk, g.partials, g.ntw, cur_stream());
 }
 
 // moe_dgemm over MXFP4 expert weights (csrc/kernels/moe_q4gemm.hip): wq uint8 [E, N, K/2] packed
@@ -771,36 +779,14 @@ void moe_q4gemm(Tensor out, Tensor a, Tensor wq, Tensor scale, Tensor sorted_ids
   TORCH_CHECK(K % akap::MXBLK == 0 && scale.dim() == 3 && scale.size(0) == E &&
                   scale.size(1) == N && scale.size(2) == K / akap::MXBLK,
               "moe_q4gemm: scale must be [E, N, K/32]");
-  TORCH_CHECK(a.size(1) == K, "moe_q4gemm: a width != K");
-  TORCH_CHECK(akap::moe_q4gemm_supported(N, K, pf, silu, splitk),
-              "moe_q4gemm: unsupported N/K/pf/split");
-  TORCH_CHECK(a.stride(0) % 8 == 0, "moe_q4gemm: 16-byte aligned rows");
-  TORCH_CHECK(bm == 32 || bm == 64, "moe_q4gemm: tile rows 32 | 64");
-  TORCH_CHECK(topk >= 1 && n_flat >= 0, "moe_q4gemm: topk >= 1, n_flat >= 0");
-  const int max_tiles = tile_expert.numel();
-  const int64_t rows = (int64_t)max_tiles * bm;
-  // split-K: out is the fp32 partials [splitk, rows, N]
-  float* partials = splitk > 1 ? o.ptr<float>(out, "out", splitk * rows * N) : nullptr;
-  void* y = splitk > 1 ? nullptr : o.bf16(out, "out");
-  TORCH_CHECK(splitk > 1 || (out.dim() == 2 && out.size(1) == (silu ? N / 2 : N)),
-              "moe_q4gemm: out width");
-  TORCH_CHECK(splitk > 1 || out.size(0) >= rows, "moe_q4gemm: out rows must cover all tiles");
-  TORCH_CHECK(gather ? a.size(0) * topk >= n_flat : a.size(0) >= rows,
-              "moe_q4gemm: a rows must cover all tiles (gather: all n_flat / topk tokens)");
-  // the non-temporal policy of moe_dgemm (one row tile per expert streams its weights once)
-  static const int nt_env = [] {
-    const char* e = std::getenv("AKAP_MOE_NT");
-    return e ? std::atoi(e) : -1;
-  }();
-  const bool ntw = nt_env >= 0 ? nt_env != 0 : (bm == 64 && n_flat <= 40 * E);
-  akap::launch_moe_q4gemm(o.bf16(a, "a", 0, kLastContig | kAlign16),
-                          o.ptr<uint8_t>(wq, "wq", E * N * (K / 2), kContig | kAlign16),
+  const MoeGemmArgs g = moe_gemm_args(o, out, a, sorted_ids, tile_expert, E, N, K,
+                                      akap::moe_q4gemm_supported(N, K, pf, silu, splitk), n_flat,
+                                      topk, gather, silu, pf, bm, splitk);
+  akap::launch_moe_q4gemm(g.a, o.ptr<uint8_t>(wq, "wq", E * N * (K / 2), kContig | kAlign16),
                           o.ptr<uint8_t>(scale, "scale", E * N * (K / akap::MXBLK),
                                          kContig | kAlign16),
-                          y, o.ptr<int32_t>(sorted_ids, "sorted_ids", rows),
-                          o.ptr<int32_t>(tile_expert, "tile_expert"), max_tiles, n_flat, topk, N,
-                          K, a.stride(0), splitk > 1 ? N : out.stride(0), gather ? 1 : 0,
-                          silu ? 1 : 0, (int)pf, (int)bm, (int)splitk, partials, ntw,
+                          g.y, g.sorted_ids, g.tile_expert, g.max_tiles, g.n_flat, g.topk, N, K,
+                          g.lda, g.ldy, g.gather, g.silu, g.pf, g.bm, g.splitk, g.partials, g.ntw,
                           cur_stream());
 }
 

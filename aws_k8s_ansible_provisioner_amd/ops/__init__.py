@@ -768,8 +768,16 @@ def fused_moe(h, w13, w2, topk_w, topk_ids, out=None):
     if not _native(h):
         out.copy_(ref.fused_moe(h, w13, w2, topk_w, topk_ids))
         return out
-    if quant:
-        return _fused_moe_quant(h, w13, w2, topk_w, topk_ids, out)
+    # the grouped GEMM op, each expert tensor's operands for it, and its ring-depth rule
+    if not quant:
+        gemm, ring, op13, op2 = torch.ops.akap.moe_dgemm, _moe_pf, (w13,), (w2,)
+    else:
+        from .quant import Mxfp4Experts
+
+        mx = isinstance(w13, Mxfp4Experts)
+        gemm = torch.ops.akap.moe_q4gemm if mx else torch.ops.akap.moe_qgemm
+        ring = _moe_qpf  # both kernels: 128-deep steps, ring depths 1 | 2 | 4
+        op13, op2 = (w13.q, w13.scale), (w2.q, w2.scale)
     n = T * K
     bm = moe_tile_rows(n, E)
     cap = moe_capacity(n, E, bm)
@@ -779,54 +787,17 @@ def fused_moe(h, w13, w2, topk_w, topk_ids, out=None):
     tile_expert = torch.empty(tiles, dtype=torch.int32, device=dev)
     sorted_ids, _, _ = moe_align(topk_ids, E, bm, inv=inv, tile_expert=tile_expert)
     act = torch.empty(cap, F, dtype=h.dtype, device=dev)
-    torch.ops.akap.moe_dgemm(act, h, w13, sorted_ids, tile_expert, n, K, True, True,
-                             _moe_pf(d), bm)
+    gemm(act, h, *op13, sorted_ids, tile_expert, n, K, True, True, ring(d), bm)
     S = moe_down_splitk(n, E, bm, F)
     if S > 1:
         # fp32 K-slices of the down projection, summed by the combine (no extra launch)
         P = torch.empty(S * cap * d, dtype=torch.float32, device=dev)
-        torch.ops.akap.moe_dgemm(P, act, w2, sorted_ids, tile_expert, n, K, False, False,
-                                 _moe_pf(F // S), bm, S)
-        torch.ops.akap.moe_combine_split(P, topk_w.contiguous(), inv, out, S, cap)
-        return out
-    y2 = torch.empty(cap, d, dtype=h.dtype, device=dev)
-    torch.ops.akap.moe_dgemm(y2, act, w2, sorted_ids, tile_expert, n, K, False, False,
-                             _moe_pf(F), bm)
-    torch.ops.akap.moe_combine(y2, topk_w.contiguous(), inv, out)
-    return out
-
-
-def _fused_moe_quant(h, w13, w2, topk_w, topk_ids, out):
-    """fused_moe's GPU pipeline over Fp8Experts or Mxfp4Experts: the same align / tile rows /
-    split choice / buffers / combines, both grouped GEMMs on moe_qgemm or moe_q4gemm."""
-    from .quant import Mxfp4Experts
-
-    mx = isinstance(w13, Mxfp4Experts)
-    gemm = torch.ops.akap.moe_q4gemm if mx else torch.ops.akap.moe_qgemm
-    ring = _moe_qpf  # both kernels: 128-deep steps, ring depths 1 | 2 | 4
-    T, d = h.shape
-    K = topk_ids.shape[1]
-    E = w13.shape[0]
-    F = w2.shape[2]
-    n = T * K
-    bm = moe_tile_rows(n, E)
-    cap = moe_capacity(n, E, bm)
-    tiles = cap // bm
-    dev = h.device
-    inv = torch.empty(n, dtype=torch.int32, device=dev)
-    tile_expert = torch.empty(tiles, dtype=torch.int32, device=dev)
-    sorted_ids, _, _ = moe_align(topk_ids, E, bm, inv=inv, tile_expert=tile_expert)
-    act = torch.empty(cap, F, dtype=h.dtype, device=dev)
-    gemm(act, h, w13.q, w13.scale, sorted_ids, tile_expert, n, K, True, True, ring(d), bm)
-    S = moe_down_splitk(n, E, bm, F)
-    if S > 1:
-        P = torch.empty(S * cap * d, dtype=torch.float32, device=dev)
-        gemm(P, act, w2.q, w2.scale, sorted_ids, tile_expert, n, K, False, False, ring(F // S),
+        gemm(P, act, *op2, sorted_ids, tile_expert, n, K, False, False, ring(F // S),
              bm, S)
         torch.ops.akap.moe_combine_split(P, topk_w.contiguous(), inv, out, S, cap)
         return out
     y2 = torch.empty(cap, d, dtype=h.dtype, device=dev)
-    gemm(y2, act, w2.q, w2.scale, sorted_ids, tile_expert, n, K, False, False, ring(F), bm)
+    gemm(y2, act, *op2, sorted_ids, tile_expert, n, K, False, False, ring(F), bm)
     torch.ops.akap.moe_combine(y2, topk_w.contiguous(), inv, out)
     return out
 

@@ -766,6 +766,31 @@ def test_exact_moe_dgemm(bm, pf, splitk, gather, silu, N, K):
     RAN["moe_dgemm"] += 1
 
 
+def test_moe_dgemm_binding_refusals():
+    """The moe_dgemm binding refuses what would read out of bounds or misaligned, as the FP8 and
+    MXFP4 bindings do.  One 32-row tile of 2 experts, N = 32, K = 64; every call is refused before
+    a kernel runs."""
+    E, N, K, bm, topk, T = 2, 32, 64, 32, 2, 8
+    n = T * topk
+    sid = torch.full((bm,), n, dtype=torch.int32, device=DEV)
+    sid[:n] = torch.arange(n, dtype=torch.int32)
+    te = torch.zeros(1, dtype=torch.int32, device=DEV)
+    a = torch.zeros(T, K, dtype=torch.bfloat16, device=DEV)
+    w = torch.zeros(E, N, K, dtype=torch.bfloat16, device=DEV)
+    out = torch.zeros(bm, N, dtype=torch.bfloat16, device=DEV)
+    call = lambda a_, topk_=topk, bm_=bm: torch.ops.akap.moe_dgemm(  # noqa: E731
+        out, a_, w, sid, te, n, topk_, True, False, 1, bm_, 1)
+    with pytest.raises(RuntimeError, match="topk >= 1"):
+        call(a, topk_=0)
+    with pytest.raises(RuntimeError, match="a rows must cover"):
+        call(a[:T - 1])                                  # gathered a one token row short
+    with pytest.raises(RuntimeError, match="tile rows 32"):
+        call(a, bm_=48)
+    off = torch.zeros(T * K + 8, dtype=torch.bfloat16, device=DEV)[1:1 + T * K].view(T, K)
+    with pytest.raises(RuntimeError, match="a must be 16-byte aligned"):
+        call(off)                                        # a offset by one element
+
+
 # ------------------------------------------------------------------------- environment knobs
 FAMILY_CASES = {
     "ring": ("test_exact_ring", RING_CASES), "lds": ("test_exact_lds", LDS_CASES),
