@@ -16,6 +16,12 @@ constexpr int kSc1 = 16;  // buffer op cache bits: sc1 (write-through stores, L1
 // Returns the 16-B unit index.
 __device__ __forceinline__ int swz8(int row, int chunk) { return row * 8 + (chunk ^ (row & 7)); }
 
+// LDS rows of 64 B = 4 chunks of 16 B (64 fp8 or 128 packed e2m1 codes: qgemm.hip, q4gemm.hip,
+// moe_q4gemm.hip): chunk c stored at c ^ g((row >> 2) & 3), g = {0, 2, 3, 1} (wgemm.hip ww_swz).
+// Returns the 16-B unit index.
+__device__ __forceinline__ int swz4_g(int row) { return (0x1320 >> (4 * ((row >> 2) & 3))) & 3; }
+__device__ __forceinline__ int swz4_w(int row, int c) { return row * 4 + (c ^ swz4_g(row)); }
+
 // LDS-DMA: 16 B per lane from g to lds_wave_base + 16 * lane.  AUX = kAuxNT is the non-temporal
 // policy: for once-read weights only (MI355X_MICROARCH.md nt-weights), never for the
 // activation rows every column tile re-reads.
@@ -25,6 +31,12 @@ __device__ __forceinline__ void glds16(const void* g, void* lds_wave_base) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
                                    (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0,
                                    AUX);
+}
+
+// LDS-DMA, 4 B per lane from g to lds_wave_base + 4 * lane
+__device__ __forceinline__ void glds4(const void* g, void* lds_wave_base) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
+                                   (__attribute__((address_space(3))) void*)lds_wave_base, 4, 0, 0);
 }
 
 // at most N_ of this wave's vector memory operations still outstanding (the counter holds 63)
@@ -37,11 +49,6 @@ __device__ __forceinline__ void wait_vm() {
 __device__ __forceinline__ float silu_bf(float g) { return bf2f(f2bf(g / (1.f + __expf(-g)))); }
 
 // ---- MXFP4 weights: q4gemm.hip, moe_q4gemm.hip ------------------------------------------------
-// LDS rows of 64 B = 4 chunks of 16 B (128 packed e2m1 codes): the 64-B-row swizzle of
-// qgemm.hip / wgemm.hip ww_swz.  Returns the 16-B unit index.
-__device__ __forceinline__ int q4swz_g(int row) { return (0x1320 >> (4 * ((row >> 2) & 3))) & 3; }
-__device__ __forceinline__ int q4swz_w(int row, int c) { return row * 4 + (c ^ q4swz_g(row)); }
-
 // 8 e2m1 codes (element e in bits [4e, 4e + 4)) times `scale` (a power of two) -> 8 bf16, exact
 __device__ __forceinline__ bf16x8 fp4x8_to_bf16x8(uint32_t v, float scale) {
   const bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, scale, 0);

@@ -160,9 +160,15 @@ inline QGemmGeom qgemm_geometry(int M, int N, int K) {
   return g;
 }
 
+// What qgemm.hip and q4gemm.hip take (qgemm_common.h): at most max_m rows, whole bk-deep wave
+// steps, 16-byte row segments of Y and 16-byte aligned rows of X and Y
+inline bool quant_gemm_supported(int M, int N, int K, int ldx, int ldy, int max_m, int bk) {
+  return M > 0 && M <= max_m && N > 0 && N % 8 == 0 && K >= bk && K % bk == 0 && ldx % 8 == 0 &&
+         ldy % 8 == 0;
+}
+
 inline bool qgemm_supported(int M, int N, int K, int ldx, int ldy) {
-  return M > 0 && M <= QGEMM_MAX_M && N > 0 && N % 8 == 0 && K >= QBK && K % QBK == 0 &&
-         ldx % 8 == 0 && ldy % 8 == 0;
+  return quant_gemm_supported(M, N, K, ldx, ldy, QGEMM_MAX_M, QBK);
 }
 
 // ---- q4gemm.hip ----
@@ -181,8 +187,7 @@ inline QGemmGeom q4gemm_geometry(int M, int N, int K) {
 // K % 128: a wave step is 128 deep, and it makes a row of scale codes (K / 32 bytes) a whole
 // number of the 4-byte words the scale DMA moves
 inline bool q4gemm_supported(int M, int N, int K, int ldx, int ldy) {
-  return M > 0 && M <= Q4GEMM_MAX_M && N > 0 && N % 8 == 0 && K >= Q4BK && K % Q4BK == 0 &&
-         ldx % 8 == 0 && ldy % 8 == 0;
+  return quant_gemm_supported(M, N, K, ldx, ldy, Q4GEMM_MAX_M, Q4BK);
 }
 
 // ---- moe_dgemm.hip / moe_qgemm.hip / moe_q4gemm.hip (moe_gemm_common.h) ----

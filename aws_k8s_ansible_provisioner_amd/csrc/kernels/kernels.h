@@ -169,7 +169,7 @@ void launch_wgemm(const WGemmArgs& p, hipStream_t st);
 struct QGemmArgs {
   const void* X;       // bf16 [M, K] (row stride ldx)
   const void* Wq;      // uint8 [N, K] contiguous, OCP e4m3fn codes
-  const float* scale;  // [N]
+  const void* scale;   // fp32 [N]
   void* Y;             // bf16 [M, N] (row stride ldy)
   int M, N, K, ldx, ldy;
 };
@@ -182,13 +182,10 @@ void launch_dequant_fp8(const void* q, const float* scale, void* out, long N, in
 // ---- q4gemm.hip: MXFP4-weight (packed e2m1 codes + e8m0 block scales) decode GEMM, M <= 256 ----
 //   Y[m,n] = bf16(sum_k X[m,k] * e2m1(Wq[n,k]) * 2^(scale[n,k/32] - 127)); no workspace, no
 //   cross-workgroup state: graph-capturable and bit-reproducible
-struct Q4GemmArgs {
-  const void* X;      // bf16 [M, K] (row stride ldx)
-  const void* Wq;     // uint8 [N, K/2] contiguous: element 2j in the low nibble of byte j
-  const void* scale;  // uint8 [N, K/32] contiguous, e8m0 codes in 2..252
-  void* Y;            // bf16 [M, N] (row stride ldy)
-  int M, N, K, ldx, ldy;
-};
+//   QGemmArgs with  Wq     uint8 [N, K/2] contiguous: element 2j in the low nibble of byte j
+//                   scale  uint8 [N, K/32] contiguous, e8m0 codes in 2..252
+// (a type of its own only so that the kernel's symbol carries its name)
+struct Q4GemmArgs : QGemmArgs {};
 // launches the tile geometry q4gemm_geometry() picks
 void launch_q4gemm(const Q4GemmArgs& p, hipStream_t st);
 // out[n, k] = bf16(e2m1(q[n, k]) * 2^(scale[n, k/32] - 127)); out bf16 [N, K], K % 32 == 0

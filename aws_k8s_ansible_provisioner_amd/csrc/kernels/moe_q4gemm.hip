@@ -107,7 +107,7 @@ __global__ __launch_bounds__(256, 2) void moe_q4gemm_kernel(const bf16* __restri
   auto sstore = [&](int q, int buf) {
     moe_sstore_a2<BM>(&lds[buf * BUF], sa[q], s_r, s_ch);
 #pragma unroll
-    for (int c = 0; c < 2; ++c) lds[buf * BUF + WOFF + q4swz_w(w_r + 64 * c, w_ch)] = sb[q][c];
+    for (int c = 0; c < 2; ++c) lds[buf * BUF + WOFF + swz4_w(w_r + 64 * c, w_ch)] = sb[q][c];
     reinterpret_cast<uint16_t*>(&lds[buf * BUF + SOFF])[tid] = (uint16_t)sc[q];
   };
   f32x4 acc[2][JN];
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(256, 2) void moe_q4gemm_kernel(const bf16* __restri
 #pragma unroll
     for (int j = 0; j < JN; ++j) {
       const int wr = wn * WCOLS + j * 16 + fr;
-      const u32x4 q4 = lds[buf * BUF + WOFF + q4swz_w(wr, fg)];
+      const u32x4 q4 = lds[buf * BUF + WOFF + swz4_w(wr, fg)];
       const float s = e8m0_to_f32((sw[wr] >> (8 * fg)) & 0xffu);
 #pragma unroll
       for (int c = 0; c < 4; ++c) {

@@ -30,15 +30,9 @@
 // = k 32 fg + 8 c .. + 8), all scaled by byte fg of the row's scale word; the A operands are
 // the X chunks 4 fg + c, i.e. chunks 4 (fg & 1) + c of half fg >> 1.  A and B agree on the
 // order, which is all an MFMA needs.
-#include "gemm_common.h"
+#include "qgemm_common.h"
 
 namespace akap {
-
-// LDS-DMA, 4 B per lane from g to lds_wave_base + 4 * lane
-__device__ __forceinline__ void glds4(const void* g, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 4, 0, 0);
-}
 
 template <int MI, int NJ, int NS>
 __global__ __launch_bounds__(256, 1) void q4gemm_kernel(Q4GemmArgs p) {
@@ -55,42 +49,21 @@ __global__ __launch_bounds__(256, 1) void q4gemm_kernel(Q4GemmArgs p) {
   static_assert(NS >= 2 && G * (NS - 1) < 63, "vmcnt counts every DMA in flight");
   __shared__ bf16x8 lds[4 * NS * SU];
 
-  const int tiles_m = (p.M + BM - 1) / BM;
-  const int tiles_n = (p.N + BN - 1) / BN;
-  const int lt = xcd_remap(blockIdx.x, tiles_m * tiles_n);
-  const int tn = lt / tiles_m, tm = lt % tiles_m;  // a column tile's row tiles share an XCD
-  const int m0 = tm * BM, n0 = tn * BN;
-  const int tid = threadIdx.x, lane = tid & 63;
-  // the wave index in a scalar register: the step count and the ring base are wave-uniform
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int fr = lane & 15, fg = lane >> 4;
-  const int nk = p.K / Q4BK;
-  const int n = w < nk ? (nk - w + 3) / 4 : 0;  // this wave's steps: k0 = (w + 4 s) * 128
+  QGEMM_TILE_PROLOGUE(Q4BK)
   const bf16* X = static_cast<const bf16*>(p.X);
   const uint8_t* Wq = static_cast<const uint8_t*>(p.Wq);
   const uint8_t* Sc = static_cast<const uint8_t*>(p.scale);
   bf16x8* ring = lds + w * NS * SU;
 
-  // per-lane DMA sources.  X: one instruction = 8 rows x 128 B of one half, lane -> row L / 8,
-  // LDS chunk L % 8 holding logical chunk (L % 8) ^ (L / 8).  Wq: one instruction = 16 rows x
-  // 64 B, lane -> row L / 4, LDS chunk L % 4 holding logical chunk (L % 4) ^ g.  Scale: lane ->
-  // tile row L.  Rows past M / N re-read row 0 (never stored).
+  // per-lane DMA sources (qgemm_common.h); the X sources are of one 64-deep half.  Scale: lane
+  // -> tile row L (lanes past BN or N re-read row 0)
   const bf16* asrc[GH];
   const uint8_t* wsrc[GW];
   const uint8_t* ssrc;
   {
-    const int lr = lane >> 3, lc = (lane & 7) ^ lr;
 #pragma unroll
-    for (int i = 0; i < GH; ++i) {
-      const int row = m0 + i * 8 + lr;
-      asrc[i] = X + (size_t)(row < p.M ? row : 0) * p.ldx + w * Q4BK + lc * 8;
-    }
-    const int wr = lane >> 2, wc = (lane & 3) ^ q4swz_g(wr);
-#pragma unroll
-    for (int j = 0; j < GW; ++j) {
-      const int v = n0 + j * 16 + wr;
-      wsrc[j] = Wq + (size_t)(v < p.N ? v : 0) * (p.K / 2) + w * (Q4BK / 2) + wc * 16;
-    }
+    for (int i = 0; i < GH; ++i) asrc[i] = qgemm_x_src<Q4BK>(X, m0 + i * 8, p.M, p.ldx, w, lane);
+    QGEMM_W_SRC(p.K / 2, Q4BK / 2)
     const int sv = n0 + lane;
     ssrc = Sc + (size_t)(lane < BN && sv < p.N ? sv : 0) * (p.K / MXBLK) + w * (Q4BK / MXBLK);
   }
@@ -107,22 +80,10 @@ __global__ __launch_bounds__(256, 1) void q4gemm_kernel(Q4GemmArgs p) {
     glds4(ssrc + k0 / MXBLK, slot + XU + WU);
   };
 
-  f32x4 acc[MI][NJ];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-#pragma unroll
-  for (int s = 0; s < NS - 1; ++s)
-    if (s < n) issue(s);
+  QGEMM_ACC(acc);
+  QGEMM_RING_PRIME(NS, n, issue);
   for (int t = 0; t < n; ++t) {
-    // retire this wave's DMAs of step t (steps t+1 .. t+NS-2 stay in flight when they exist);
-    // the reads below are of this wave's own DMAs, so no barrier is needed
-    if (t + NS - 2 < n) wait_vm<G * (NS - 2)>();
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // step t-1's fragment reads returned
-    if (t + NS - 1 < n) issue(t + NS - 1);              // ... so its slot can be refilled
+    QGEMM_RING_ADVANCE(NS, G, t, n, issue);
     const bf16x8* slot = ring + (t % NS) * SU;
     const bf16x8* xh = slot + (fg >> 1) * (BM * 8);     // this lane group's 64-deep half
     const u32x4* wslot = reinterpret_cast<const u32x4*>(slot + XU);
@@ -134,7 +95,7 @@ __global__ __launch_bounds__(256, 1) void q4gemm_kernel(Q4GemmArgs p) {
       for (int i = 0; i < MI; ++i) a[c][i] = xh[swz8(i * 16 + fr, 4 * (fg & 1) + c)];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-      const u32x4 q = wslot[q4swz_w(j * 16 + fr, fg)];
+      const u32x4 q = wslot[swz4_w(j * 16 + fr, fg)];
       const float sc = e8m0_to_f32((sslot[j * 16 + fr] >> (8 * fg)) & 0xffu);
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
@@ -146,42 +107,9 @@ __global__ __launch_bounds__(256, 1) void q4gemm_kernel(Q4GemmArgs p) {
     }
   }
 
-  // ---- sum the 4 waves' partial tiles through LDS: part[w][row][PB] fp32 ----
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();  // no wave reads or fills its ring any more
   float* part = reinterpret_cast<float*>(lds);
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        part[(w * BM + i * 16 + fg * 4 + r) * PB + j * 16 + fr] = acc[i][j][r];
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-
-  // bf16 + 16-byte row-segment stores (N % 8 == 0: a segment is inside N or outside)
-  bf16* Y = static_cast<bf16*>(p.Y);
-  constexpr int CPR = BN / 8;
-  for (int e = tid; e < BM * CPR; e += 256) {
-    const int rr = e / CPR, cc = e % CPR;
-    const int row = m0 + rr, col = n0 + cc * 8;
-    if (row >= p.M || col >= p.N) continue;
-    f32x4 lo = *reinterpret_cast<const f32x4*>(&part[rr * PB + cc * 8]);
-    f32x4 hi = *reinterpret_cast<const f32x4*>(&part[rr * PB + cc * 8 + 4]);
-#pragma unroll
-    for (int ww = 1; ww < 4; ++ww) {
-      lo += *reinterpret_cast<const f32x4*>(&part[(ww * BM + rr) * PB + cc * 8]);
-      hi += *reinterpret_cast<const f32x4*>(&part[(ww * BM + rr) * PB + cc * 8 + 4]);
-    }
-    bf16x8 o;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      o[q] = f2bf(lo[q]);
-      o[4 + q] = f2bf(hi[q]);
-    }
-    *reinterpret_cast<bf16x8*>(Y + (size_t)row * p.ldy + col) = o;
-  }
+  qgemm_combine(part, acc, w, fr, fg);
+  QGEMM_STORE_EPILOGUE(false)  // the block scales were applied in the K loop
 }
 
 void launch_q4gemm(const Q4GemmArgs& p, hipStream_t st) {
@@ -223,9 +151,7 @@ void launch_dequant_mxfp4(const void* q, const void* scale, void* out, long N, i
                           hipStream_t st) {
   const long blocks = N * (K / MXBLK);
   if (blocks == 0) return;
-  const long wgs = (blocks + 255) / 256;
-  const int grid = (int)(wgs < 8192 ? wgs : 8192);
-  dequant_mxfp4_kernel<<<grid, 256, 0, st>>>(static_cast<const uint8_t*>(q),
+  dequant_mxfp4_kernel<<<dequant_grid(blocks), 256, 0, st>>>(static_cast<const uint8_t*>(q),
                                              static_cast<const uint8_t*>(scale),
                                              static_cast<bf16*>(out), blocks);
 }

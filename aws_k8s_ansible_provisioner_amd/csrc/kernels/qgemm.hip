@@ -25,15 +25,11 @@
 // ds_read_b128 of the fp8 row gives the B operands of both MFMAs (low 8 bytes, high 8 bytes)
 // and the A operands are X chunks 2 fg and 2 fg + 1.  A and B agree on the order, which is all
 // an MFMA needs.
-#include "gemm_common.h"
+#include "qgemm_common.h"
 
 namespace akap {
 
-// X rows (128 B) use swz8.  W rows of 64 B: chunk c stored at c ^ g((row >> 2) & 3),
-// g = {0, 2, 3, 1} (wgemm.hip ww_swz)
-__device__ __forceinline__ int qswz_g(int row) { return (0x1320 >> (4 * ((row >> 2) & 3))) & 3; }
-__device__ __forceinline__ int qswz_w(int row, int c) { return row * 4 + (c ^ qswz_g(row)); }
-
+// X rows (128 B) use swz8, W rows of 64 B swz4_w (gemm_common.h)
 template <int MI, int NJ, int NS>
 __global__ __launch_bounds__(256, 1) void qgemm_kernel(QGemmArgs p) {
   constexpr int BM = 16 * MI, BN = 16 * NJ;
@@ -46,41 +42,16 @@ __global__ __launch_bounds__(256, 1) void qgemm_kernel(QGemmArgs p) {
   static_assert(NS >= 3, "two steps in flight");
   __shared__ bf16x8 lds[4 * NS * SU];
 
-  const int tiles_m = (p.M + BM - 1) / BM;
-  const int tiles_n = (p.N + BN - 1) / BN;
-  const int lt = xcd_remap(blockIdx.x, tiles_m * tiles_n);
-  const int tn = lt / tiles_m, tm = lt % tiles_m;  // a column tile's row tiles share an XCD
-  const int m0 = tm * BM, n0 = tn * BN;
-  const int tid = threadIdx.x, lane = tid & 63;
-  // the wave index in a scalar register: the step count and the ring base are wave-uniform
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int fr = lane & 15, fg = lane >> 4;
-  const int nk = p.K / QBK;
-  const int n = w < nk ? (nk - w + 3) / 4 : 0;  // this wave's steps: k0 = (w + 4 s) * 64
+  QGEMM_TILE_PROLOGUE(QBK)
   const bf16* X = static_cast<const bf16*>(p.X);
   const uint8_t* Wq = static_cast<const uint8_t*>(p.Wq);
   bf16x8* ring = lds + w * NS * SU;
 
-  // per-lane DMA sources.  X: one instruction = 8 rows x 128 B, lane -> row L / 8, LDS chunk
-  // L % 8 holding logical chunk (L % 8) ^ (L / 8).  Wq: one instruction = 16 rows x 64 B, lane
-  // -> row L / 4, LDS chunk L % 4 holding logical chunk (L % 4) ^ g.  Rows past M / N re-read
-  // row 0 (never stored).
-  const bf16* asrc[GA];
+  const bf16* asrc[GA];  // per-lane DMA sources (qgemm_common.h)
   const uint8_t* wsrc[GW];
-  {
-    const int lr = lane >> 3, lc = (lane & 7) ^ lr;
 #pragma unroll
-    for (int i = 0; i < GA; ++i) {
-      const int row = m0 + i * 8 + lr;
-      asrc[i] = X + (size_t)(row < p.M ? row : 0) * p.ldx + w * QBK + lc * 8;
-    }
-    const int wr = lane >> 2, wc = (lane & 3) ^ qswz_g(wr);
-#pragma unroll
-    for (int j = 0; j < GW; ++j) {
-      const int v = n0 + j * 16 + wr;
-      wsrc[j] = Wq + (size_t)(v < p.N ? v : 0) * p.K + w * QBK + wc * 16;
-    }
-  }
+  for (int i = 0; i < GA; ++i) asrc[i] = qgemm_x_src<QBK>(X, m0 + i * 8, p.M, p.ldx, w, lane);
+  QGEMM_W_SRC(p.K, QBK)
   auto issue = [&](int s) {
     bf16x8* slot = ring + (s % NS) * SU;
     const int k0 = s * 4 * QBK;
@@ -91,22 +62,10 @@ __global__ __launch_bounds__(256, 1) void qgemm_kernel(QGemmArgs p) {
     for (int j = 0; j < GW; ++j) glds16<kAuxNT>(wsrc[j] + k0, slot + BM * 8 + j * 64);
   };
 
-  f32x4 acc[MI][NJ];
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-#pragma unroll
-  for (int s = 0; s < NS - 1; ++s)
-    if (s < n) issue(s);
+  QGEMM_ACC(acc);
+  QGEMM_RING_PRIME(NS, n, issue);
   for (int t = 0; t < n; ++t) {
-    // retire this wave's DMAs of step t (steps t+1 .. t+NS-2 stay in flight when they exist);
-    // the reads below are of this wave's own DMAs, so no barrier is needed
-    if (t + NS - 2 < n) wait_vm<G * (NS - 2)>();
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // step t-1's fragment reads returned
-    if (t + NS - 1 < n) issue(t + NS - 1);              // ... so its slot can be refilled
+    QGEMM_RING_ADVANCE(NS, G, t, n, issue);
     const bf16x8* slot = ring + (t % NS) * SU;
     const u32x4* wslot = reinterpret_cast<const u32x4*>(slot + BM * 8);
     bf16x8 a0[MI], a1[MI];
@@ -117,7 +76,7 @@ __global__ __launch_bounds__(256, 1) void qgemm_kernel(QGemmArgs p) {
     }
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-      const u32x4 q = wslot[qswz_w(j * 16 + fr, fg)];
+      const u32x4 q = wslot[swz4_w(j * 16 + fr, fg)];
       const bf16x8 b0 = fp8x8_to_bf16x8(q[0], q[1]);
       const bf16x8 b1 = fp8x8_to_bf16x8(q[2], q[3]);
 #pragma unroll
@@ -128,44 +87,9 @@ __global__ __launch_bounds__(256, 1) void qgemm_kernel(QGemmArgs p) {
     }
   }
 
-  // ---- sum the 4 waves' partial tiles through LDS: part[w][row][PB] fp32 ----
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();  // no wave reads or fills its ring any more
   float* part = reinterpret_cast<float*>(lds);
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        part[(w * BM + i * 16 + fg * 4 + r) * PB + j * 16 + fr] = acc[i][j][r];
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-
-  // scale + bf16 + 16-byte row-segment stores (N % 8 == 0: a segment is inside N or outside)
-  bf16* Y = static_cast<bf16*>(p.Y);
-  constexpr int CPR = BN / 8;
-  for (int e = tid; e < BM * CPR; e += 256) {
-    const int rr = e / CPR, cc = e % CPR;
-    const int row = m0 + rr, col = n0 + cc * 8;
-    if (row >= p.M || col >= p.N) continue;
-    f32x4 lo = *reinterpret_cast<const f32x4*>(&part[rr * PB + cc * 8]);
-    f32x4 hi = *reinterpret_cast<const f32x4*>(&part[rr * PB + cc * 8 + 4]);
-#pragma unroll
-    for (int ww = 1; ww < 4; ++ww) {
-      lo += *reinterpret_cast<const f32x4*>(&part[(ww * BM + rr) * PB + cc * 8]);
-      hi += *reinterpret_cast<const f32x4*>(&part[(ww * BM + rr) * PB + cc * 8 + 4]);
-    }
-    const f32x4 s0 = *reinterpret_cast<const f32x4*>(p.scale + col);
-    const f32x4 s1 = *reinterpret_cast<const f32x4*>(p.scale + col + 4);
-    bf16x8 o;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      o[q] = f2bf(lo[q] * s0[q]);
-      o[4 + q] = f2bf(hi[q] * s1[q]);
-    }
-    *reinterpret_cast<bf16x8*>(Y + (size_t)row * p.ldy + col) = o;
-  }
+  qgemm_combine(part, acc, w, fr, fg);
+  QGEMM_STORE_EPILOGUE(true)
 }
 
 void launch_qgemm(const QGemmArgs& p, hipStream_t st) {
@@ -217,9 +141,7 @@ void launch_dequant_fp8(const void* q, const float* scale, void* out, long N, in
                         hipStream_t st) {
   const long chunks = N * (K / 16);
   if (chunks == 0) return;
-  const long blocks = (chunks + 255) / 256;
-  const int grid = (int)(blocks < 8192 ? blocks : 8192);
-  dequant_fp8_kernel<<<grid, 256, 0, st>>>(static_cast<const uint8_t*>(q), scale,
+  dequant_fp8_kernel<<<dequant_grid(chunks), 256, 0, st>>>(static_cast<const uint8_t*>(q), scale,
                                            static_cast<bf16*>(out), chunks, K / 16);
 }
 

@@ -471,22 +471,36 @@ void wgemm(Tensor out, Tensor x, Tensor w) {
   akap::launch_wgemm(a, cur_stream());
 }
 
+// What qgemm and q4gemm share: x [M, K] and out [M, N] bf16 with 16-byte aligned rows.  The
+// caller has checked the dimension counts, read (N, K) from its weight and checked its scale's
+// shape; it passes its *_supported predicate and what that needs, and fills Wq and scale.
+static akap::QGemmArgs qgemm_args(const OpArgs& o, const Tensor& out, const Tensor& x, int N,
+                                  int K, bool (*supported)(int, int, int, int, int),
+                                  const char* needs) {
+  const char* op = o.op();
+  const int M = x.size(0);
+  TORCH_CHECK(x.size(1) == K && out.size(0) == M && out.size(1) == N, op, ": shapes");
+  TORCH_CHECK(M == 0 || supported(M, N, K, x.stride(0), out.stride(0)), op, ": needs ", needs);
+  akap::QGemmArgs a{};
+  a.X = o.bf16(x, "x", 0, kLastContig | kAlign16);
+  a.Y = o.bf16(out, "out", 0, kLastContig | kAlign16);
+  a.M = M; a.N = N; a.K = K;
+  a.ldx = x.stride(0); a.ldy = out.stride(0);
+  return a;
+}
+
 // FP8-weight decode GEMM (csrc/kernels/qgemm.hip): out[M, N] = bf16(scale[n] * x[M, K] @
 // float(wq[N, K])^T), wq = OCP e4m3fn bytes (uint8 or float8_e4m3fn), scale fp32 per channel.
 void qgemm(Tensor out, Tensor x, Tensor wq, Tensor scale) {
   const OpArgs o = on_gpu("qgemm", x, "x");
   TORCH_CHECK(x.dim() == 2 && wq.dim() == 2 && out.dim() == 2 && scale.dim() == 1,
               "qgemm: x, wq, out 2-D and scale 1-D");
-  const int M = x.size(0), N = wq.size(0), K = wq.size(1);
-  TORCH_CHECK(x.size(1) == K && out.size(0) == M && out.size(1) == N && scale.size(0) == N,
-              "qgemm: shapes");
-  TORCH_CHECK(M == 0 || akap::qgemm_supported(M, N, K, x.stride(0), out.stride(0)),
-              "qgemm: needs M <= 256, K % 64 == 0, N % 8 == 0 and 16-byte aligned rows");
-  akap::QGemmArgs a{o.bf16(x, "x", 0, kLastContig | kAlign16),
-                    o.ptr(wq, "wq", {at::kByte, at::kFloat8_e4m3fn}, 0, kContig | kAlign16),
-                    o.ptr<float>(scale, "scale", N, kContig | kAlign16),
-                    o.bf16(out, "out", 0, kLastContig | kAlign16),
-                    M, N, K, (int)x.stride(0), (int)out.stride(0)};
+  const int N = wq.size(0), K = wq.size(1);
+  TORCH_CHECK(scale.size(0) == N, "qgemm: shapes");
+  akap::QGemmArgs a = qgemm_args(o, out, x, N, K, akap::qgemm_supported,
+                                 "M <= 256, K % 64 == 0, N % 8 == 0 and 16-byte aligned rows");
+  a.Wq = o.ptr(wq, "wq", {at::kByte, at::kFloat8_e4m3fn}, 0, kContig | kAlign16);
+  a.scale = o.ptr<float>(scale, "scale", N, kContig | kAlign16);
   akap::launch_qgemm(a, cur_stream());
 }
 
@@ -509,19 +523,14 @@ void q4gemm(Tensor out, Tensor x, Tensor wq, Tensor scale) {
   const OpArgs o = on_gpu("q4gemm", x, "x");
   TORCH_CHECK(x.dim() == 2 && wq.dim() == 2 && out.dim() == 2 && scale.dim() == 2,
               "q4gemm: x, wq, scale and out 2-D");
-  const int M = x.size(0), N = wq.size(0), K = 2 * wq.size(1);
-  TORCH_CHECK(x.size(1) == K && out.size(0) == M && out.size(1) == N, "q4gemm: shapes");
+  const int N = wq.size(0), K = 2 * wq.size(1);
   TORCH_CHECK(K % akap::MXBLK == 0 && scale.size(0) == N && scale.size(1) == K / akap::MXBLK,
               "q4gemm: scale must be [N, K/32]");
-  TORCH_CHECK(M == 0 || akap::q4gemm_supported(M, N, K, x.stride(0), out.stride(0)),
-              "q4gemm: needs M <= 256, K >= 128, K % 128 == 0, N % 8 == 0 and 16-byte aligned "
-              "rows");
-  akap::Q4GemmArgs a{o.bf16(x, "x", 0, kLastContig | kAlign16),
-                     o.ptr<uint8_t>(wq, "wq", (int64_t)N * (K / 2), kContig | kAlign16),
-                     o.ptr<uint8_t>(scale, "scale", (int64_t)N * (K / akap::MXBLK),
-                                    kContig | kAlign16),
-                     o.bf16(out, "out", 0, kLastContig | kAlign16),
-                     M, N, K, (int)x.stride(0), (int)out.stride(0)};
+  akap::Q4GemmArgs a{qgemm_args(o, out, x, N, K, akap::q4gemm_supported,
+                                "M <= 256, K >= 128, K % 128 == 0, N % 8 == 0 and 16-byte "
+                                "aligned rows")};
+  a.Wq = o.ptr<uint8_t>(wq, "wq", (int64_t)N * (K / 2), kContig | kAlign16);
+  a.scale = o.ptr<uint8_t>(scale, "scale", (int64_t)N * (K / akap::MXBLK), kContig | kAlign16);
   akap::launch_q4gemm(a, cur_stream());
 }
 

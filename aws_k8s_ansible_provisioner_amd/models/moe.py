@@ -39,9 +39,7 @@ import torch
 import torch.nn.functional as F
 
 from .. import ops
-from ..ops.quant import (Fp8Experts, Fp8Weight, Mxfp4Experts, Mxfp4Weight, QuantExperts,
-                         dequant_experts, quantize_fp8, quantize_fp8_experts, quantize_mxfp4,
-                         quantize_mxfp4_experts)
+from ..ops.quant import FORMATS, QuantExperts, dequant_experts, quantize_experts
 from ..parallel import comm
 from ..parallel.state import ParallelState
 
@@ -142,7 +140,7 @@ class MoEBlock:
         """Replace this rank's expert weights (its local experts in ep mode, its F shard in tp
         mode) by Fp8Experts, one tensor at a time: each bf16 tensor is dropped before the next
         quantized one is made.  The router stays bf16."""
-        self._quantize(Fp8Experts, quantize_fp8_experts)
+        self.quantize(FORMATS["fp8"])
 
     def check_mxfp4_shapes(self) -> None:
         """The 4-bit grouped GEMM (csrc/kernels/moe_q4gemm.hip) reads 4 scale codes per weight
@@ -159,17 +157,20 @@ class MoEBlock:
     @torch.no_grad()
     def quantize_mxfp4(self) -> None:
         """quantize_fp8 for Mxfp4Experts (the OCP MX rule per 32-block, quantize_mxfp4)."""
-        self.check_mxfp4_shapes()
-        self._quantize(Mxfp4Experts, quantize_mxfp4_experts)
+        self.quantize(FORMATS["mxfp4"])
 
-    def _quantize(self, kind, quantizer) -> None:
+    @torch.no_grad()
+    def quantize(self, fmt) -> None:
+        """The same for any QuantFormat."""
+        if fmt.name == "mxfp4":
+            self.check_mxfp4_shapes()
         for name in ("w13", "w2"):
             w = getattr(self, name)
-            if isinstance(w, QuantExperts) and not isinstance(w, kind):
+            if isinstance(w, QuantExperts) and not isinstance(w, fmt.Experts):
                 raise ValueError(f"{name} is already {type(w).__name__}")
-            if not isinstance(w, kind):
+            if not isinstance(w, fmt.Experts):
                 setattr(self, name, None)
-                q = quantizer(w)
+                q = quantize_experts(w, fmt)
                 del w
                 setattr(self, name, q)
 
@@ -193,25 +194,29 @@ class MoEBlock:
         return (prefix + "block_sparse_moe.gate.weight", p + "w1.weight", p + "w3.weight",
                 p + "w2.weight")
 
-    def _load_fp8(self, prefix: str, proj) -> None:
-        """Expert weights of a checkpoint as Fp8Experts.  proj(key) is the projection `key`.weight:
-        an Fp8Weight for a pre-quantized tensor with a per-channel or per-tensor `weight_scale`
-        (kept bit for bit; gate and up are concatenated along N with their scales), else a
-        plain or (block-scaled source) fp32 tensor, quantized per channel here."""
+    def _load_quantized(self, prefix: str, proj, fmt) -> None:
+        """Expert weights of a checkpoint as fmt's expert container.  proj(key) is the
+        projection `key`.weight: fmt's 2-D weight for a pre-quantized tensor (kept bit for bit;
+        gate and up are concatenated along N with their scales; an MXFP4 TP shard slices F on
+        whole scale blocks), else a plain or (block-scaled FP8 source) fp32 tensor, quantized
+        here."""
+        if fmt.name == "mxfp4":
+            self.check_mxfp4_shapes()
         r = self.ps.tp_rank
         d, fl = self.cfg.hidden_size, self.f_local
         fs = slice(None) if self.mode == "ep" else slice(r * fl, (r + 1) * fl)
 
-        def q8(parts: list) -> Fp8Weight:
-            if all(isinstance(p, Fp8Weight) for p in parts):
-                return Fp8Weight(torch.cat([p.q for p in parts], 0),
-                                 torch.cat([p.scale for p in parts], 0))
-            return quantize_fp8(torch.cat([p.float() for p in parts], 0).to(self.device))
+        def quant(parts: list):
+            if all(isinstance(p, fmt.Weight) for p in parts):
+                return fmt.Weight.cat(parts)
+            return fmt.quantize(torch.cat([p.float() for p in parts], 0).to(self.device))
 
         def fill(name: str, N: int, K: int, expert) -> None:
             setattr(self, name, None)  # drop the old tensor before the new one is resident
-            q = torch.empty(self.e_local, N, K, dtype=torch.uint8, device=self.device)
-            s = torch.empty(self.e_local, N, dtype=torch.float32, device=self.device)
+            q = torch.empty(self.e_local, N, K // fmt.per_byte, dtype=torch.uint8,
+                            device=self.device)
+            s = torch.empty(fmt.scale_shape((self.e_local, N), K), dtype=fmt.scale_dtype,
+                            device=self.device)
             for j in range(self.e_local):
                 w = expert(self.e0 + j)
                 if tuple(w.shape) != (N, K):
@@ -219,56 +224,21 @@ class MoEBlock:
                                      f"{tuple(w.shape)} != model {(N, K)}")
                 q[j].copy_(w.q)
                 s[j].copy_(w.scale)
-            setattr(self, name, Fp8Experts(q, s))
+            setattr(self, name, fmt.Experts(q, s, check=False))  # each part was checked
 
         key = lambda n: n[:-len(".weight")]  # noqa: E731
         names = lambda e: self._hf_names(prefix, e)  # noqa: E731
-        fill("w13", 2 * fl, d, lambda e: q8([proj(key(names(e)[1]))[fs],
-                                             proj(key(names(e)[2]))[fs]]))
-        fill("w2", d, fl, lambda e: q8([proj(key(names(e)[3]))[:, fs]]))
+        fill("w13", 2 * fl, d, lambda e: quant([proj(key(names(e)[1]))[fs],
+                                                proj(key(names(e)[2]))[fs]]))
+        fill("w2", d, fl, lambda e: quant([proj(key(names(e)[3]))[:, fs]]))
 
-    def _load_mxfp4(self, prefix: str, proj) -> None:
-        """Expert weights of a checkpoint as Mxfp4Experts.  proj(key) is the projection
-        `key`.weight: an Mxfp4Weight for packed uint8 [N, K/2] codes with uint8 `weight_scale`
-        [N, K/32] (kept bit for bit; gate and up are concatenated along N with their scales; a
-        TP shard slices F on whole scale blocks), else a plain tensor, quantized here."""
-        self.check_mxfp4_shapes()
-        r = self.ps.tp_rank
-        d, fl = self.cfg.hidden_size, self.f_local
-        fs = slice(None) if self.mode == "ep" else slice(r * fl, (r + 1) * fl)
-
-        def q4(parts: list) -> Mxfp4Weight:
-            if all(isinstance(p, Mxfp4Weight) for p in parts):
-                return Mxfp4Weight(torch.cat([p.q for p in parts], 0),
-                                   torch.cat([p.scale for p in parts], 0), check=False)
-            return quantize_mxfp4(torch.cat([p.float() for p in parts], 0).to(self.device))
-
-        def fill(name: str, N: int, K: int, expert) -> None:
-            setattr(self, name, None)  # drop the old tensor before the new one is resident
-            q = torch.empty(self.e_local, N, K // 2, dtype=torch.uint8, device=self.device)
-            s = torch.empty(self.e_local, N, K // 32, dtype=torch.uint8, device=self.device)
-            for j in range(self.e_local):
-                w = expert(self.e0 + j)
-                if tuple(w.shape) != (N, K):
-                    raise ValueError(f"{prefix}expert {self.e0 + j} {name}: checkpoint shape "
-                                     f"{tuple(w.shape)} != model {(N, K)}")
-                q[j].copy_(w.q)
-                s[j].copy_(w.scale)
-            setattr(self, name, Mxfp4Experts(q, s, check=False))  # each part was checked
-
-        key = lambda n: n[:-len(".weight")]  # noqa: E731
-        names = lambda e: self._hf_names(prefix, e)  # noqa: E731
-        fill("w13", 2 * fl, d, lambda e: q4([proj(key(names(e)[1]))[fs],
-                                             proj(key(names(e)[2]))[fs]]))
-        fill("w2", d, fl, lambda e: q4([proj(key(names(e)[3]))[:, fs]]))
-
-    def load_state_dict(self, sd: dict, prefix: str, fp8_proj=None, kind: str = "fp8") -> None:
-        """fp8_proj: with expert quantization on, the checkpoint accessor (DecoderLM) through
-        which the experts are loaded as Fp8Experts or (kind "mxfp4") Mxfp4Experts."""
+    def load_state_dict(self, sd: dict, prefix: str, proj=None, fmt=None) -> None:
+        """proj, fmt: with expert quantization on, the checkpoint accessor (DecoderLM) through
+        which the experts are loaded and the QuantFormat they are loaded as."""
         r, tp = self.ps.tp_rank, self.ps.tp_size
         self.router.copy_(sd[self._hf_names(prefix, 0)[0]])
-        if fp8_proj is not None:
-            (self._load_mxfp4 if kind == "mxfp4" else self._load_fp8)(prefix, fp8_proj)
+        if proj is not None:
+            self._load_quantized(prefix, proj, fmt)
             return
         for j in range(self.e_local):
             e = self.e0 + j
@@ -288,21 +258,11 @@ class MoEBlock:
         sd = {self._hf_names(prefix, 0)[0]: self.router.clone()}
         for e in range(self.E):
             _, n1, n3, n2 = self._hf_names(prefix, e)
-            if isinstance(self.w13, Mxfp4Experts):
-                # packed uint8 codes + uint8 e8m0 weight_scale [N, K/32], the dense MXFP4 form
-                for n, w in ((n1, self.w13[e][:Fn]), (n3, self.w13[e][Fn:]), (n2, self.w2[e])):
-                    sd[n] = w.q.clone()
-                    sd[n[:-len(".weight")] + ".weight_scale"] = w.scale.clone()
-                continue
-            if self.quantized:
-                # float8_e4m3fn codes + [N, 1] fp32 weight_scale, as DecoderLM.hf_state_dict
-                for n, w in ((n1, self.w13[e][:Fn]), (n3, self.w13[e][Fn:]), (n2, self.w2[e])):
-                    sd[n] = w.q.clone().view(torch.float8_e4m3fn)
-                    sd[n[:-len(".weight")] + ".weight_scale"] = w.scale.clone().reshape(-1, 1)
-                continue
-            sd[n1] = self.w13[e, :Fn].clone()
-            sd[n3] = self.w13[e, Fn:].clone()
-            sd[n2] = self.w2[e].clone()
+            for n, w in ((n1, self.w13[e][:Fn]), (n3, self.w13[e][Fn:]), (n2, self.w2[e])):
+                if self.quantized:  # the format's checkpoint form, as DecoderLM.hf_state_dict
+                    sd[n], sd[n[:-len(".weight")] + ".weight_scale"] = w.hf_export()
+                else:
+                    sd[n] = w.clone()
         return sd
 
     def forward(self, h: torch.Tensor) -> torch.Tensor:

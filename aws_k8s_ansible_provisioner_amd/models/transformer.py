@@ -22,8 +22,7 @@ import torch.nn.functional as F
 
 from .. import ops
 from ..ops import reference as ref
-from ..ops.quant import (Fp8Weight, Mxfp4Weight, QuantWeight, quantize_fp8, quantize_mxfp4,
-                         reserve_scratch)
+from ..ops.quant import FORMATS, Fp8Weight, Mxfp4Weight, QuantWeight, reserve_scratch
 from ..parallel import comm
 from ..parallel.state import ParallelState, get_state
 from .config import ModelConfig
@@ -85,14 +84,13 @@ def _shard_cols(w, rank: int, size: int):
 PROJECTIONS = ("w_qkv", "w_o", "w_gate_up", "w_down")
 QUANTIZATIONS = (None, "fp8", "mxfp4")
 EXPERT_QUANTIZATIONS = (None, "fp8", "mxfp4")  # MoE expert weights only (ops.quant.QuantExperts)
-_QUANTIZERS = {"fp8": quantize_fp8, "mxfp4": quantize_mxfp4}
 _FP8_BLOCK = 128  # block-scaled checkpoints: one weight_scale_inv per 128 x 128 block
 
 
 def _scale_kind(t: torch.Tensor) -> str:
     """Which quantization a checkpoint's `weight_scale` tensor belongs to: e8m0 codes (uint8)
     are MXFP4 block scales, anything else an FP8 scale."""
-    return "mxfp4" if t.dtype in (torch.uint8, getattr(torch, "float8_e8m0fnu", None)) else "fp8"
+    return "mxfp4" if t.dtype in FORMATS["mxfp4"].ckpt_scale_dtypes else "fp8"
 
 
 def _checkpoint_proj(sd: dict, key: str, quantization: Optional[str]):
@@ -104,7 +102,7 @@ def _checkpoint_proj(sd: dict, key: str, quantization: Optional[str]):
     dequantized to fp32 here and re-quantized per channel by the caller.  `input_scale`
     (activation scales of W8A8 checkpoints) is not used: activations stay bf16."""
     w = sd[key + ".weight"]
-    if w.dtype in (torch.uint8, getattr(torch, "float4_e2m1fn_x2", None)):
+    if w.dtype in FORMATS["mxfp4"].ckpt_dtypes:
         if quantization != "mxfp4":
             raise ValueError(f"{key}.weight holds packed 4-bit codes: this is an MXFP4 "
                              f"checkpoint, load it with --quantization mxfp4")
@@ -112,7 +110,7 @@ def _checkpoint_proj(sd: dict, key: str, quantization: Optional[str]):
             raise ValueError(f"{key}.weight is MXFP4 but the checkpoint has no "
                              f"{key}.weight_scale")
         return Mxfp4Weight(w, sd[key + ".weight_scale"])  # refuses e8m0 codes outside 2..252
-    if w.dtype != torch.float8_e4m3fn:
+    if w.dtype not in FORMATS["fp8"].ckpt_dtypes:
         return w
     if quantization != "fp8":
         raise ValueError(f"{key}.weight is float8_e4m3fn: this is an FP8 checkpoint, load it "
@@ -136,11 +134,8 @@ def _checkpoint_proj(sd: dict, key: str, quantization: Optional[str]):
 def _fuse_rows(parts: list):
     """Concatenate projections along the output channels: bit-exact for pre-quantized parts
     (codes and per-channel scales are concatenated), fp32 otherwise."""
-    if all(isinstance(p, Fp8Weight) for p in parts):
-        return Fp8Weight(torch.cat([p.q for p in parts], 0), torch.cat([p.scale for p in parts], 0))
-    if all(isinstance(p, Mxfp4Weight) for p in parts):
-        return Mxfp4Weight(torch.cat([p.q for p in parts], 0),
-                           torch.cat([p.scale for p in parts], 0), check=False)
+    if isinstance(parts[0], QuantWeight) and all(type(p) is type(parts[0]) for p in parts):
+        return type(parts[0]).cat(parts)
     if any(isinstance(p, QuantWeight) or p.dtype == torch.float32 for p in parts):
         return torch.cat([p.float() for p in parts], 0)
     return torch.cat(parts, 0)
@@ -342,7 +337,7 @@ class DecoderLM:
         bf16 (`quantized` stays false: the dense-layer logic is untouched).  Also reserves the
         dequantization scratch the prefill path uses, sized to the largest expert tensor
         (E_local * 2F * d elements)."""
-        self._quantize_experts("fp8")
+        self._quantize_experts(FORMATS["fp8"])
 
     @torch.no_grad()
     def quantize_mxfp4_experts(self) -> None:
@@ -350,17 +345,17 @@ class DecoderLM:
         with one e8m0 scale per 32 elements along K), on each rank's local experts or F shard,
         which must be a multiple of 128 (MoEBlock.check_mxfp4_shapes).  The scratch is the same
         size: it holds the dequantized bf16 tensor."""
-        self._quantize_experts("mxfp4")
+        self._quantize_experts(FORMATS["mxfp4"])
 
-    def _quantize_experts(self, kind: str) -> None:
+    def _quantize_experts(self, fmt) -> None:
         if not self.cfg.is_moe:
             raise ValueError(f"{self.cfg.name}: a dense model has no experts to quantize")
         largest = 0
         for lw in self.layers:
             if lw.moe is not None:
-                lw.moe.quantize_mxfp4() if kind == "mxfp4" else lw.moe.quantize_fp8()
+                lw.moe.quantize(fmt)
                 largest = max(largest, lw.moe.w13.numel(), lw.moe.w2.numel())
-        self.expert_quantization = kind
+        self.expert_quantization = fmt.name
         self.experts_quantized = True
         reserve_scratch(largest, self.device)
 
@@ -390,7 +385,7 @@ class DecoderLM:
                 w = getattr(lw, name)
                 if not isinstance(w, QuantWeight):
                     setattr(lw, name, None)
-                    w = _QUANTIZERS[kind](w)
+                    w = FORMATS[kind].quantize(w)
                     setattr(lw, name, w)
                 largest = max(largest, w.numel())
         self.quantization = kind
@@ -412,14 +407,10 @@ class DecoderLM:
         q, kv = self.hq * D, self.hkv * D
 
         def put(key: str, w, a: int = 0, b: Optional[int] = None) -> None:
-            # rows [a, b) of a projection; quantized: float8_e4m3fn codes + [N, 1] fp32 scales,
-            # or packed e2m1 codes uint8 [N, K/2] + e8m0 codes uint8 [N, K/32]
-            if isinstance(w, Mxfp4Weight):
-                sd[key + ".weight"] = w.q[a:b].clone()
-                sd[key + ".weight_scale"] = w.scale[a:b].clone()
-            elif isinstance(w, Fp8Weight):
-                sd[key + ".weight"] = w.q[a:b].clone().view(torch.float8_e4m3fn)
-                sd[key + ".weight_scale"] = w.scale[a:b].clone().reshape(-1, 1)
+            # rows [a, b) of a projection; quantized: its format's checkpoint form
+            # (QuantFormat.export)
+            if isinstance(w, QuantWeight):
+                sd[key + ".weight"], sd[key + ".weight_scale"] = w[a:b].hf_export()
             else:
                 sd[key + ".weight"] = w[a:b].clone()
 
@@ -456,7 +447,7 @@ class DecoderLM:
             return
         setattr(lw, name, None)  # drop the old weight before the new one is resident
         if not isinstance(src, QuantWeight):
-            src = _QUANTIZERS[self.quantization](src.to(self.device))
+            src = FORMATS[self.quantization].quantize(src.to(self.device))
         setattr(lw, name, src.to(self.device))
         self.quantized = True
         reserve_scratch(src.numel(), self.device)
@@ -517,7 +508,7 @@ class DecoderLM:
                 cp(lw.q_norm, sd[p + "self_attn.q_norm.weight"])
                 cp(lw.k_norm, sd[p + "self_attn.k_norm.weight"])
             if lw.moe is not None:
-                lw.moe.load_state_dict(sd, p, fp8_proj=eproj, kind=eq or "fp8")
+                lw.moe.load_state_dict(sd, p, proj=eproj, fmt=FORMATS.get(eq))
                 if eproj is not None:
                     self.experts_quantized = True
                     reserve_scratch(max(lw.moe.w13.numel(), lw.moe.w2.numel()), self.device)

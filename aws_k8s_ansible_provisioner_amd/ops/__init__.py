@@ -772,10 +772,7 @@ def fused_moe(h, w13, w2, topk_w, topk_ids, out=None):
     if not quant:
         gemm, ring, op13, op2 = torch.ops.akap.moe_dgemm, _moe_pf, (w13,), (w2,)
     else:
-        from .quant import Mxfp4Experts
-
-        mx = isinstance(w13, Mxfp4Experts)
-        gemm = torch.ops.akap.moe_q4gemm if mx else torch.ops.akap.moe_qgemm
+        gemm = getattr(torch.ops.akap, w13.fmt.moe_gemm)
         ring = _moe_qpf  # both kernels: 128-deep steps, ring depths 1 | 2 | 4
         op13, op2 = (w13.q, w13.scale), (w2.q, w2.scale)
     n = T * K
