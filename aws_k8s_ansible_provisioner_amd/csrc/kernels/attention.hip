@@ -24,10 +24,12 @@
 //    r3_attn_fused_breakdown.log).
 //  * Prefill: grid (q-tile, kv_head); each wave walks the causal range of its rows.
 #include <cstdlib>
+#include <stdexcept>
 #include <type_traits>
 
 #include "common.h"
 #include "kernels.h"
+#include "kv_write.h"
 
 namespace akap {
 
@@ -212,14 +214,8 @@ __device__ __forceinline__ void load_q(bf16x8 (&qb)[kNC], const bf16* qrow_ptr, 
 // row G+1 = its value head; 16 threads per row, 8 dims each.  q rows -> per-head RMSNorm
 // (bf16-rounded, like the standalone kernel) -> NeoX RoPE -> LDS; the new token's k / v
 // (only when write_kv) -> paged cache.  Rotary pairs (d, d+64) sit in threads j and j^8.
-// V tail image helper: 16 threads (j = dims [8j, 8j+8)) hold an 8-token group token-major
-// (rows[i] = token i) and store it as the cache's [D][8] group image (dim-major, 16 B per dim)
-__device__ __forceinline__ void group_units(const bf16x8 (&rows)[8], bf16x8 (&u)[8]) {
-#pragma unroll
-  for (int k = 0; k < 8; ++k)
-#pragma unroll
-    for (int i = 0; i < 8; ++i) u[k][i] = rows[i][k];
-}
+// The row arithmetic and the K / V stores are kv_write.h's (shared with the rider workgroups of
+// the gate|up GEMM launch); group_units there builds the V tail's [D][8] group image.
 
 // Fused-prologue operands loaded up front (grid decode kernel).  Every prologue load is
 // issued BEFORE the first K/V chunk's loads, so the prologue's waits (counted vmcnt: the
@@ -291,25 +287,7 @@ __device__ __forceinline__ void fused_qkv_prologue_pre(const AttnParams& p, int 
     for (int i = 0; i < 8; ++i) x[i] = bf2f(pp.raw[i]);
     if (rr <= G) {
       const bf16* nw = rr < G ? p.q_w : p.k_w;
-      if (nw != nullptr) {
-        float ss = 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) ss += x[i] * x[i];
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 16);
-        const float inv = rsqrtf(ss / (float)kD + p.eps);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) x[i] = bf2f(f2bf(x[i] * inv * bf2f(pp.w8[i])));
-      }
-      const float cv[8] = {pp.c0[0], pp.c0[1], pp.c0[2], pp.c0[3],
-                           pp.c1[0], pp.c1[1], pp.c1[2], pp.c1[3]};
-      const float sv[8] = {pp.s0[0], pp.s0[1], pp.s0[2], pp.s0[3],
-                           pp.s1[0], pp.s1[1], pp.s1[2], pp.s1[3]};
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const float other = __shfl_xor(x[i], 8, 16);
-        x[i] = j < 8 ? x[i] * cv[i] - other * sv[i] : x[i] * cv[i] + other * sv[i];
-      }
+      head_norm_rope(x, nw != nullptr, pp.w8, pp.c0, pp.c1, pp.s0, pp.s1, p.eps, j);
     }
     bf16x8 o8;
 #pragma unroll
@@ -320,24 +298,24 @@ __device__ __forceinline__ void fused_qkv_prologue_pre(const AttnParams& p, int 
       const int64_t slot = pp.slot;
       if (slot >= 0) {
         // tail path with defer_kv: only the LDS images here, the cache / tail stores are
-        // issued at the end of the work item (deferred_kv_stores)
-        const bool gst = !(tail && p.defer_kv);
+        // issued at the end of the work item (deferred_kv_stores) -- or, with
+        // kAttnCallerWritesKv, by the caller's rider workgroups and not here at all
+        const bool gst = !(tail && (p.defer_kv || (p.flags & kAttnCallerWritesKv)));
         const int64_t blk = slot / p.BS;
         const int off = (int)(slot % p.BS);
         if (rr == G) {
-          const size_t e = ((size_t)blk * p.Hkv + kvh) * p.BS * kD + k_swz_offset(off) +
-                           k_dim_offset(8 * j);
           if constexpr (F8) {
+            const size_t e = ((size_t)blk * p.Hkv + kvh) * p.BS * kD + k_swz_offset(off) +
+                             k_dim_offset(8 * j);
             uint32_t* dst = reinterpret_cast<uint32_t*>((uint8_t*)p.k_cache + e);
             dst[0] = f32x4_to_fp8x4((float)o8[0], (float)o8[1], (float)o8[2], (float)o8[3]);
             dst[1] = f32x4_to_fp8x4((float)o8[4], (float)o8[5], (float)o8[6], (float)o8[7]);
           } else {
-            if (gst) *reinterpret_cast<bf16x8*>((bf16*)p.k_cache + e) = o8;
+            if (gst) kv_store_k((bf16*)p.k_cache, p.Hkv, p.BS, kvh, slot, j, o8);
             if (tail) *reinterpret_cast<bf16x8*>(k_img + 8 * j) = o8;
           }
         } else if (tail) {
           const int i0 = off & 7;
-          bf16* tb = p.v_tail + ((size_t)pp.tsl * p.Hkv + kvh) * 8 * kD + 8 * j;
           bf16x8 rows[8], u[8];
 #pragma unroll
           for (int i = 0; i < 8; ++i)
@@ -347,12 +325,9 @@ __device__ __forceinline__ void fused_qkv_prologue_pre(const AttnParams& p, int 
           for (int k = 0; k < 8; ++k) *reinterpret_cast<bf16x8*>(v_img + (8 * j + k) * 8) = u[k];
           if (!gst) {
           } else if (i0 == 7) {
-            bf16* e = (bf16*)p.v_cache + ((size_t)blk * p.Hkv + kvh) * kD * p.BS +
-                      (off >> 3) * kD * 8 + (size_t)(8 * j) * 8;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) *reinterpret_cast<bf16x8*>(e + 8 * k) = u[k];
+            kv_store_v_group((bf16*)p.v_cache, p.Hkv, p.BS, kvh, slot, j, u);
           } else {
-            *reinterpret_cast<bf16x8*>(tb + (size_t)i0 * kD) = o8;
+            kv_store_v_tail_row(p.v_tail, p.Hkv, kvh, pp.tsl, i0, j, o8);
           }
         } else {
           const size_t e = ((size_t)blk * p.Hkv + kvh) * kD * p.BS + (off >> 3) * kD * 8 + (off & 7);
@@ -390,29 +365,22 @@ __device__ __forceinline__ void deferred_kv_stores(const AttnParams& p, int kvh,
   const int j = threadIdx.x & 15;
   const int G = p.G;
   if (rr != G && rr != G + 1) return;
-  const int64_t blk = pp.slot / p.BS;
-  const int off = (int)(pp.slot % p.BS);
   if (rr == G) {
-    const size_t e = ((size_t)blk * p.Hkv + kvh) * p.BS * kD + k_swz_offset(off) +
-                     k_dim_offset(8 * j);
-    *reinterpret_cast<bf16x8*>((bf16*)p.k_cache + e) =
-        *reinterpret_cast<const bf16x8*>(k_img + 8 * j);
+    kv_store_k((bf16*)p.k_cache, p.Hkv, p.BS, kvh, pp.slot, j,
+               *reinterpret_cast<const bf16x8*>(k_img + 8 * j));
     return;
   }
-  const int i0 = off & 7;
+  const int i0 = (int)(pp.slot % p.BS) & 7;
   if (i0 == 7) {  // the group is complete: its [D][8] image goes to the cache
-    bf16* e = (bf16*)p.v_cache + ((size_t)blk * p.Hkv + kvh) * kD * p.BS + (off >> 3) * kD * 8 +
-              (size_t)(8 * j) * 8;
+    bf16x8 u[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k)
-      *reinterpret_cast<bf16x8*>(e + 8 * k) =
-          *reinterpret_cast<const bf16x8*>(v_img + (8 * j + k) * 8);
+    for (int k = 0; k < 8; ++k) u[k] = *reinterpret_cast<const bf16x8*>(v_img + (8 * j + k) * 8);
+    kv_store_v_group((bf16*)p.v_cache, p.Hkv, p.BS, kvh, pp.slot, j, u);
   } else {  // the token's row (dims 8j..8j+7) goes to the sequence's V tail
     bf16x8 o8;
 #pragma unroll
     for (int i = 0; i < 8; ++i) o8[i] = v_img[(8 * j + i) * 8 + i0];
-    bf16* tb = p.v_tail + ((size_t)pp.tsl * p.Hkv + kvh) * 8 * kD + 8 * j;
-    *reinterpret_cast<bf16x8*>(tb + (size_t)i0 * kD) = o8;
+    kv_store_v_tail_row(p.v_tail, p.Hkv, kvh, pp.tsl, i0, j, o8);
   }
 }
 
@@ -610,7 +578,8 @@ __device__ __forceinline__ void decode_item(const AttnParams& p, int seq, int kv
     }
   }
   if constexpr (FUSED && !F8) {
-    if (use_img && p.defer_kv) deferred_kv_stores<F8>(p, kvh, pp, k_img, v_img);
+    if (use_img && p.defer_kv && !(p.flags & kAttnCallerWritesKv))
+      deferred_kv_stores<F8>(p, kvh, pp, k_img, v_img);
   }
 #undef OS
 }
@@ -1190,6 +1159,11 @@ void launch_paged_attn_prefill(const AttnParams& p, int num_tiles, int tile_rows
 
 void launch_paged_attn_decode(const AttnParams& p, int num_seqs, hipStream_t s) {
   if (num_seqs == 0) return;
+  // the caller's writer covers the fused bf16 V-tail form only (kv_write.h); anything else would
+  // leave the token unwritten
+  if ((p.flags & kAttnCallerWritesKv) && (p.kv_fp8 || p.v_tail == nullptr || p.qkv == nullptr))
+    throw std::invalid_argument(
+        "paged_attn_decode: kAttnCallerWritesKv needs the fused form, bf16 caches and a V tail");
   const size_t smem = (size_t)(4 * p.G * (kD + 4) + 8 * p.G) * sizeof(float) +
                       (p.qkv ? (size_t)p.G * kD * sizeof(bf16) : 0) +
                       (p.v_tail ? (size_t)kD * 8 * sizeof(bf16) : 0) +

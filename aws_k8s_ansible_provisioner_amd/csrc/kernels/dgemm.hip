@@ -34,6 +34,7 @@
 #include <cstdlib>
 
 #include "gemm_common.h"
+#include "kv_write.h"
 
 namespace akap {
 
@@ -52,6 +53,14 @@ __global__ __launch_bounds__(256, 2) void dgemm_kernel(DGemmArgs p) {
 
   const int tiles_n = (p.N + DBN - 1) / DBN;
   const int tiles_m = (p.M + DBM - 1) / DBM;
+  if constexpr (PRO == PRO_PLAIN && EPI == EPI_SILU && SPL == 0) {
+    // K/V rider workgroups behind the tiles (gdgemm.hip, kv_write.h): return before any staging
+    if ((int)blockIdx.x >= tiles_n * tiles_m) {
+      kv_rider_block(p.kv, (int)blockIdx.x - tiles_n * tiles_m,
+                     (int)gridDim.x - tiles_n * tiles_m);
+      return;
+    }
+  }
   const int lt = xcd_remap(blockIdx.x, tiles_n * tiles_m);
   const int tn = lt / tiles_m;
   const int tm = lt % tiles_m;
@@ -550,7 +559,8 @@ void launch_dgemm(const DGemmArgs& a, int pro, int splitk, int pf, hipStream_t s
     return;
   }
   const int tiles = ((a.M + DBM - 1) / DBM) * ((a.N + DBN - 1) / DBN);
-  dim3 grid(tiles, splitk);
+  const int riders = pro == PRO_PLAIN && p.epi == EPI_SILU && splitk == 1 ? p.kv.n_blocks : 0;
+  dim3 grid(tiles + riders, splitk);
   if (splitk > 1 && p.counters != nullptr && pro == PRO_PLAIN &&
       (splitk == 2 || splitk == 4 || splitk == 8)) {  // in-launch combine
     if (splitk == 2) dgemm_main<2, 2>(p, grid, pro, p.epi, pf, st);

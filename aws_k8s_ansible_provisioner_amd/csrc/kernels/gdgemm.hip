@@ -38,6 +38,7 @@
 //          launch, so the GEMM -> reduce kernel boundary (~1.5 us) and the reduce body go away,
 //          and split-K becomes legal for the SwiGLU epilogue too.
 #include "gemm_common.h"
+#include "kv_write.h"
 
 namespace akap {
 
@@ -78,6 +79,15 @@ __global__ __launch_bounds__(64 * NW, OCC) void gdgemm_kernel(DGemmArgs p) {
   const int tiles_n = (p.N + BN - 1) / BN;
   const int tiles_m = (p.M + GBM - 1) / GBM;
   const int ntiles = tiles_n * tiles_m;
+  if constexpr (EPI == EPI_SILU && SPL == 0) {
+    // rider workgroups behind the tiles (launch_gdgemm appended p.kv.n_blocks of them): the
+    // decode step's new-token K / V write, on CUs / slots the tiles leave free.  They return
+    // before any staging or barrier; the tiles' own path below is unchanged.
+    if ((int)blockIdx.x >= ntiles) {
+      kv_rider_block(p.kv, (int)blockIdx.x - ntiles, (int)gridDim.x - ntiles);
+      return;
+    }
+  }
   const int lt = xcd_remap(blockIdx.x, ntiles);
   const int tn = lt / tiles_m, tm = lt % tiles_m;
   const int m0 = tm * GBM, n0 = tn * BN;
@@ -332,7 +342,10 @@ static void gdgemm_ring(const DGemmArgs& p, dim3 grid, int splitk, hipStream_t s
 void launch_gdgemm(const DGemmArgs& p, int splitk, hipStream_t st) {
   const int bm = (p.bm == 128 || p.bm == 256) ? p.bm : 64;
   const int tiles = ((p.M + bm - 1) / bm) * ((p.N + p.bn - 1) / p.bn);
-  dim3 grid(tiles, splitk);
+  // K/V riders (kv_write.h): SwiGLU epilogue, one K slice; the caller sized n_blocks by
+  // kv_rider_blocks (host_contract.h)
+  const int riders = p.epi == EPI_SILU && splitk == 1 ? p.kv.n_blocks : 0;
+  dim3 grid(tiles + riders, splitk);
   const bool deep = p.ns >= 6;
   if (bm == 256) {  // 256-row tiles, 8 waves: 3 x 48 KB (BN 128) / 3 x 40 KB (BN 64) ring
     if (p.bn == 128) gdgemm_ring<128, 3, 1, 256, 8>(p, grid, splitk, st);

@@ -276,4 +276,36 @@ inline DGemmContract dgemm_contract(int M, int N, int K, int pro, int epi, int s
   return c;
 }
 
+// ---- K/V rider workgroups of the gate|up decode GEMM launch (kv_write.h) ----
+// Workgroups of one dgemm.hip / gdgemm.hip variant a CU holds at once: the register ring is
+// __launch_bounds__(256, 2); the LDS ring holds two only in its shallow 64-row form (the deep
+// ring and the 128 / 256-row tiles fill a CU's LDS with one).
+inline int dgemm_wgs_per_cu(int bn, int ns, int bm) {
+  if (bn == 0) return 2;
+  if (bm == 128 || bm == 256) return 1;
+  return ns >= 6 ? 1 : 2;
+}
+
+constexpr int kKvRiderRows = 16;  // (sequence, kv head, K | V) rows one rider covers per pass
+
+// Rider workgroups to append to the launch, 0 when it may carry none.  Legal: the SwiGLU
+// epilogue with one K slice on the register-ring or LDS-ring family, and the kernel's resident
+// capacity (cus x workgroups per CU) covers the tiles and at least one rider, so no rider waits
+// for a tile to finish; the model side: bf16 KV cache with a V tail, tp = 1, a dense layer, no
+// weight quantization.  Each rider loops over its share of the ceil(B * Hkv * 2 / 16) passes.
+inline int kv_rider_blocks(int M, int N, int epi, int splitk, int bn, int ns, int bm, int cus,
+                           int B, int Hkv, bool kv_bf16_tail, int tp, bool dense,
+                           bool quantized) {
+  if (epi != EPI_SILU || splitk != 1 || bn == 256 || bn < 0) return 0;
+  if (!kv_bf16_tail || tp != 1 || !dense || quantized) return 0;
+  if (M <= 0 || N <= 0 || B <= 0 || Hkv <= 0 || cus <= 0) return 0;
+  const int tile_n = bn > 0 ? bn : DBN, tile_m = bn > 0 ? bm : DBM;
+  if (tile_m <= 0) return 0;
+  const long tiles = (long)((M + tile_m - 1) / tile_m) * ((N + tile_n - 1) / tile_n);
+  const long room = (long)cus * dgemm_wgs_per_cu(bn, ns, bm) - tiles;
+  const long need = ((long)B * Hkv * 2 + kKvRiderRows - 1) / kKvRiderRows;
+  const long n = need < room ? need : room;
+  return n > 0 ? (int)n : 0;
+}
+
 }  // namespace akap

@@ -52,7 +52,7 @@ struct AttnParams {
   float* part_m;  // [B, Hkv, parts, G]
   float* part_l;
   float* part_o;  // [B, Hkv, parts, G, D]
-  int flags;      // reserved (0)
+  int flags;      // kAttnCallerWritesKv | 0
   int kv_fp8;     // caches hold OCP e4m3fn bytes (scale 1) instead of bf16
   // fused decode (qkv != nullptr): the kernel itself applies per-head q/k RMSNorm + RoPE to
   // the raw QKV projection row and writes the new token's K/V into the paged cache
@@ -80,6 +80,11 @@ struct AttnParams {
   // launch_paged_attn_decode: AKAP_DECODE_DEFER_KV, default 1)
   int defer_kv;
 };
+// AttnParams::flags bit: the caller writes the new token's K / V (the riders of the gate|up GEMM
+// launch, KvWriteArgs below).  The fused decode kernel still builds its LDS images of the token
+// and attends to it from them, but issues none of the V-tail path's cache / tail stores.  bf16
+// caches with a V tail only (launch_paged_attn_decode refuses anything else).
+constexpr int kAttnCallerWritesKv = 1;
 // tile_rows: 128 -> flash-style LDS-tiled kernel (4 waves), 256 -> its 8-wave form (bf16 KV)
 void launch_paged_attn_prefill(const AttnParams& p, int num_tiles, int tile_rows, hipStream_t s);
 void launch_paged_attn_decode(const AttnParams& p, int num_seqs, hipStream_t s);
@@ -95,6 +100,27 @@ void launch_gemm_bf16(const void* X, const void* W, void* Y, float* ws, int M, i
 // Fused decode GEMM: A-operand prologue (PRO_*) folded into the MFMA GEMM's staging, and an
 // epilogue (EPI_*) doing a decode layer's residual add + next-norm elementwise half, or SwiGLU.
 // Split-K partials (+ per-row sums of squares) are reduced by a second pass with the same epilogue.
+// The decode step's new-token K / V write carried by a GEMM launch (kv_write.h): n_blocks
+// "rider" workgroups appended to the grid write, for each of the B sequences and Hkv kv heads,
+// the K row (per-head RMSNorm + RoPE of the raw QKV row) and the V row (tail row, or the whole
+// 8-token group when the token completes it) that the fused decode attention would have
+// written.  bf16 caches with a V tail.  n_blocks == 0: off.
+struct KvWriteArgs {
+  const void* qkv;           // bf16 [B, qkv_stride]: q heads | k heads | v heads
+  int qkv_stride;
+  const int64_t* positions;  // [B]
+  const int64_t* slots;      // [B] (-1: no write)
+  const float* cos_sin;      // [max_pos, D] = cos | sin
+  const void* k_w;           // bf16 [D] or nullptr
+  float eps;
+  void* k_cache;             // bf16 [NB, Hkv, BS, D]
+  void* v_cache;             // bf16 [NB, Hkv, BS/8, D, 8]
+  void* v_tail;              // bf16 [slots, Hkv, 8, D]
+  const int* tail_slot;      // [B] (-1: no write)
+  int Hq, Hkv, BS, B;
+  int n_blocks;              // rider workgroups (each loops over its share of the rows)
+};
+
 struct DGemmArgs {
   // bf16 tensors (void* so this header stays free of device types)
   const void* X;     // A source: [M, K] (PLAIN/ADDNORM) or [M, 2K] = [gate | up] (SILU)
@@ -116,6 +142,9 @@ struct DGemmArgs {
   int bm;         // gdgemm tile rows: 64 (default) | 128 (with bn = 128)
   int ntw;        // weight DMA policy: -1 default (gdgemm nt, kgemm not), 1 both nt, 0 neither
   int stag;       // 1: each workgroup walks its K range from a tile-dependent offset (wrapping)
+  // EPI_SILU launches of dgemm.hip / gdgemm.hip with one K slice: rider workgroups behind the
+  // tiles (kv_rider_blocks of host_contract.h)
+  KvWriteArgs kv;
 };
 // process default for DGemmArgs::ntw (AKAP_WEIGHT_NT, read once)
 int weight_nt_default();

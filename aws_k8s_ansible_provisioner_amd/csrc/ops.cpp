@@ -295,7 +295,7 @@ void paged_attention_decode_fused(Tensor out, Tensor qkv, Tensor k_cache, Tensor
                                   std::optional<Tensor> k_w, Tensor part_m, Tensor part_l,
                                   Tensor part_o, int64_t num_parts, int64_t part_size, int64_t G,
                                   double scale, double eps, std::optional<Tensor> v_tail,
-                                  std::optional<Tensor> tail_slot) {
+                                  std::optional<Tensor> tail_slot, bool write_kv) {
   const OpArgs a = on_gpu("paged_attention_decode_fused", qkv, "qkv");
   const KVCache kv = kv_cache_of(a, k_cache, v_cache);
   const int B = seq_lens.numel();
@@ -308,6 +308,12 @@ void paged_attention_decode_fused(Tensor out, Tensor qkv, Tensor k_cache, Tensor
   set_raw_qkv(a, p, qkv, B, positions, cos_sin, q_w, k_w, eps);
   p.slots = a.ptr<int64_t>(slots, "slots", B);
   p.q_start = nullptr;
+  if (!write_kv) {
+    // the caller writes the new token's K / V (dgemm kv_write): the V-tail form only
+    TORCH_CHECK(!kv.fp8 && vt.v_tail != nullptr, a.op(),
+                ": write_kv=False needs a bf16 KV cache and a V tail");
+    p.flags |= akap::kAttnCallerWritesKv;
+  }
   set_split_kv(a, p, part_m, part_l, part_o, num_parts, part_size, B);
   akap::launch_paged_attn_decode(p, B, cur_stream());
 }
@@ -403,11 +409,59 @@ static akap::DGemmArgs dgemm_args(const OpArgs& o, const Tensor& out, const Tens
   return a;
 }
 
+// kv_write of dgemm(): [qkv, positions, slots, cos_sin, k_w (no elements: no k norm), k_cache,
+// v_cache, v_tail, tail_slot] of the decode step whose new-token K / V rows rider workgroups of
+// this launch write (kernels/kv_write.h), one row of each per sequence: B = positions.numel().
+// blocks > 0 caps the riders (1: one rider loops over every row).  The launch must be one the
+// riders are legal on (kv_rider_blocks of host_contract.h): asking otherwise is an error, not a
+// launch that quietly leaves the cache unwritten.
+static akap::KvWriteArgs kv_write_args(const OpArgs& o, const std::vector<Tensor>& t, int64_t Hq,
+                                       int64_t blocks, double eps, int M, int N, int pro, int epi,
+                                       int splitk, int bn, int ns, int bm, int cus) {
+  TORCH_CHECK(t.size() == 9, o.op(), ": kv_write takes 9 tensors");
+  const Tensor &qkv = t[0], &positions = t[1], &slots = t[2], &cos_sin = t[3], &k_w = t[4];
+  const KVCache kv = kv_cache_of(o, t[5], t[6]);
+  const int B = positions.numel();
+  const VTail vt = v_tail_of(o, kv, t[7], t[8], B);
+  TORCH_CHECK(!kv.fp8 && t[7].size(0) >= 1, o.op(), ": kv_write needs a bf16 KV cache");
+  TORCH_CHECK(Hq > 0 && qkv.dim() == 2 && qkv.size(0) >= B &&
+                  qkv.size(1) >= (Hq + 2 * kv.Hkv) * 128 && qkv.stride(0) % 8 == 0,
+              o.op(), ": kv_write qkv must be [>= B, >= (Hq + 2 Hkv) * 128] in 16-byte rows");
+  TORCH_CHECK(cos_sin.dim() == 2 && cos_sin.size(1) == 128, o.op(),
+              ": kv_write cos_sin must be contiguous fp32 [max_pos, 128]");
+  TORCH_CHECK(k_w.numel() == 0 || k_w.numel() == 128, o.op(), ": kv_write k_w must be bf16 [128]");
+  const int room = pro == akap::PRO_PLAIN
+                       ? akap::kv_rider_blocks(M, N, epi, splitk, bn, ns, bm, cus, B, kv.Hkv, true,
+                                               1, true, false)
+                       : 0;
+  TORCH_CHECK(room > 0, o.op(), ": this launch cannot carry K/V riders (kv_rider_blocks)");
+  akap::KvWriteArgs k{};
+  k.qkv = o.bf16(qkv, "kv_write qkv", 0, kLastContig | kAlign16);
+  k.qkv_stride = qkv.stride(0);
+  k.positions = o.ptr<int64_t>(positions, "kv_write positions", B);
+  k.slots = o.ptr<int64_t>(slots, "kv_write slots", B);
+  k.cos_sin = o.ptr<float>(cos_sin, "kv_write cos_sin");
+  k.k_w = k_w.numel() ? o.bf16(k_w, "kv_write k_w", 128) : nullptr;
+  k.eps = (float)eps;
+  k.k_cache = kv.k;
+  k.v_cache = kv.v;
+  k.v_tail = vt.v_tail;
+  k.tail_slot = vt.tail_slot;
+  k.Hq = (int)Hq;
+  k.Hkv = kv.Hkv;
+  k.BS = kv.BS;
+  k.B = B;
+  k.n_blocks = blocks > 0 && blocks < room ? (int)blocks : room;
+  return k;
+}
+
 void dgemm(Tensor out, Tensor x, Tensor w, Tensor ws, int64_t pro, int64_t splitk, int64_t pf,
            std::optional<Tensor> r, std::optional<Tensor> rout, std::optional<Tensor> ln,
            double eps, int64_t epi, std::optional<Tensor> ss_in, std::optional<Tensor> ss_out,
            std::optional<Tensor> aout, std::optional<Tensor> ln_out, int64_t bn, int64_t ns,
-           std::optional<Tensor> counters, int64_t bm) {
+           std::optional<Tensor> counters, int64_t bm,
+           std::optional<std::vector<Tensor>> kv_write,
+           int64_t kv_hq, int64_t kv_blocks, double kv_eps) {
   TORCH_CHECK(pro >= 0 && pro <= 2, "dgemm: prologue 0|1|2");
   TORCH_CHECK(epi >= 0 && epi <= 2, "dgemm: epilogue 0|1|2");
   const OpArgs o = on_gpu("dgemm", x, "x");
@@ -449,6 +503,10 @@ void dgemm(Tensor out, Tensor x, Tensor w, Tensor ws, int64_t pro, int64_t split
     a.ln = o.bf16(*ln, "ln");
     TORCH_CHECK(a.R != a.Rout, "dgemm: rout must not alias r");
   }
+  if (kv_write.has_value())
+    a.kv = kv_write_args(o, *kv_write, kv_hq, kv_blocks, kv_eps, M, N, (int)pro, (int)epi,
+                         (int)splitk, (int)bn, (int)ns, (int)bm,
+                         device_cus(x.device().index()));
   if (c.family == akap::DG_PGEMM_SK) {
     akap::launch_pgemm_sk(a, (int)splitk, cur_stream());
     return;
@@ -1311,7 +1369,7 @@ TORCH_LIBRARY(akap, m) {
       "Tensor(c!) v_cache, Tensor block_tables, Tensor seq_lens, Tensor positions, Tensor slots, "
       "Tensor cos_sin, Tensor? q_w, Tensor? k_w, Tensor(d!) part_m, Tensor(e!) part_l, "
       "Tensor(f!) part_o, int num_parts, int part_size, int G, float scale, float eps, "
-      "Tensor(g!)? v_tail=None, Tensor? tail_slot=None) -> ()");
+      "Tensor(g!)? v_tail=None, Tensor? tail_slot=None, bool write_kv=True) -> ()");
   m.def(
       "sample(Tensor logits, Tensor temperature, Tensor top_k, Tensor top_p, Tensor seeds, "
       "Tensor steps, Tensor(a!) out_tokens, Tensor(b!) out_logprobs, "
@@ -1328,7 +1386,8 @@ TORCH_LIBRARY(akap, m) {
       "dgemm(Tensor(a!) out, Tensor x, Tensor w, Tensor(b!) ws, int pro, int splitk, int pf, "
       "Tensor? r=None, Tensor(c!)? rout=None, Tensor? ln=None, float eps=1e-6, int epi=0, "
       "Tensor? ss_in=None, Tensor(d!)? ss_out=None, Tensor(e!)? aout=None, "
-      "Tensor? ln_out=None, int bn=0, int ns=0, Tensor(f!)? counters=None, int bm=64) -> ()");
+      "Tensor? ln_out=None, int bn=0, int ns=0, Tensor(f!)? counters=None, int bm=64, "
+      "Tensor[]? kv_write=None, int kv_hq=0, int kv_blocks=0, float kv_eps=1e-6) -> ()");
   m.def("wgemm(Tensor(a!) out, Tensor x, Tensor w) -> ()");
   m.def("qgemm(Tensor(a!) out, Tensor x, Tensor wq, Tensor scale) -> ()");
   m.def("dequant_fp8(Tensor(a!) out, Tensor wq, Tensor scale) -> ()");

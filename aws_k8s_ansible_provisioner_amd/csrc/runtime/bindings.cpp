@@ -96,6 +96,9 @@ static void bind_contract(py::module_ m) {
     const DGemmContract c = dgemm_contract(M, N, K, pro, epi, splitk, pf, bn, ns, bm, inlaunch, cus);
     return py::make_tuple(c.supported, c.family, c.inlaunch, c.ws_floats, c.ticket_ints);
   });
+  m.attr("KV_RIDER_ROWS") = kKvRiderRows;
+  m.def("dgemm_wgs_per_cu", &dgemm_wgs_per_cu);
+  m.def("kv_rider_blocks", &kv_rider_blocks);
 }
 
 #ifndef AKAP_RT_HASH

@@ -34,6 +34,10 @@ FUSED_GEMM = os.environ.get("AKAP_FUSED_GEMM", "1") != "0"
 # prefill attention applies the q norm + RoPE itself from the QKV rows (AKAP_PREFILL_QPREP=0:
 # the standalone pass writes every q row, the kernel reads q)
 PREFILL_QPREP = os.environ.get("AKAP_PREFILL_QPREP", "1") != "0"
+# fused decode chain: the new token's K/V rows are written by rider workgroups of the gate|up
+# GEMM launch instead of by the attention kernel, when that launch has resident room for them
+# (ops.kv_rider_blocks; AKAP_DECODE_KV_RIDER=0: always by the attention kernel)
+DECODE_KV_RIDER = os.environ.get("AKAP_DECODE_KV_RIDER", "1") != "0"
 
 
 @dataclasses.dataclass
@@ -693,6 +697,12 @@ class DecoderLM:
             ss = torch.zeros(2 * L, T, dtype=torch.float32, device=self.device)
             a1 = ops.rms_norm(residual, self.layers[0].ln1, eps)
             ss_in = None
+        # K/V riders: bf16 cache with a V tail, tp = 1 (this path is dense and unquantized), and
+        # the planned gate|up variant has resident room behind its tiles
+        rider = (DECODE_KV_RIDER and tp == 1 and batch.v_tails is not None
+                 and batch.tail_slot is not None and k_caches[0].dtype == torch.bfloat16
+                 and ops.kv_rider_blocks(T, self.layers[0].w_gate_up.shape[0],
+                                         plan["w_gate_up"], T, self.hkv) > 0)
         for li, lw in enumerate(self.layers):
             nxt = self.layers[li + 1].w_qkv if li + 1 < L else None
             qkv = ops.dgemm(a1, lw.w_qkv, eps=eps, ss_in=ss_in, variant=plan["w_qkv"])
@@ -705,7 +715,7 @@ class DecoderLM:
                 self.hq // self.hkv, self.scale, eps, workspace=batch.workspace,
                 num_parts=batch.num_parts, part_size=batch.part_size,
                 v_tail=batch.v_tails[li] if batch.v_tails is not None else None,
-                tail_slot=batch.tail_slot)
+                tail_slot=batch.tail_slot, write_kv=not rider)
             a2 = torch.empty_like(residual)
             if tp > 1:
                 part = ops.dgemm(attn.view(T, self.hq * self.D), lw.w_o, eps=eps,
@@ -715,8 +725,11 @@ class DecoderLM:
                 ops.dgemm(attn.view(T, self.hq * self.D), lw.w_o, eps=eps, out=residual,
                           epi=ops.EPI_RESNORM, ss_out=ss[2 * li], a_out=a2, ln_out=lw.ln2,
                           variant=plan["w_o"])
+            kvw = ops.KvWrite(qkv, batch.positions, batch.slots, self.cos_sin, lw.k_norm,
+                              k_caches[li], v_caches[li], batch.v_tails[li], batch.tail_slot,
+                              self.hq, eps) if rider else None
             act = ops.dgemm(a2, lw.w_gate_up, eps=eps, ss_in=ss[2 * li], epi=ops.EPI_SILU,
-                            variant=plan["w_gate_up"])
+                            variant=plan["w_gate_up"], kv_write=kvw)
             if li + 1 < L:
                 a1 = torch.empty_like(residual)
                 if tp > 1:

@@ -13,7 +13,7 @@ Layouts shared with the kernels (see csrc/kernels/rope_cache.hip):
 from __future__ import annotations
 
 import os
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -241,11 +241,14 @@ def paged_attention_decode(out, q, k_cache, v_cache, block_tables, seq_lens, gqa
 def paged_attention_decode_fused(out, qkv, k_cache, v_cache, block_tables, seq_lens, positions,
                                  slots, cos_sin, q_w, k_w, gqa_group: int, scale: float,
                                  eps: float, workspace=None, num_parts: int = 1,
-                                 part_size: int = 512, v_tail=None, tail_slot=None):
+                                 part_size: int = 512, v_tail=None, tail_slot=None,
+                                 write_kv: bool = True):
     """Decode attention that consumes the raw QKV projection: per-head q/k RMSNorm + RoPE
     and the new token's K/V cache write happen inside the attention kernel.
     out [B, Hq, D]; qkv [B, (Hq + 2 Hkv) * D].  With v_tail (bf16 cache) the new token's V
-    goes to its sequence's tail row and the cache gets whole 8-token groups only."""
+    goes to its sequence's tail row and the cache gets whole 8-token groups only.
+    write_kv=False (bf16 cache with v_tail): the kernel attends to the new token but leaves
+    its K/V write to the caller -- `dgemm(..., kv_write=KvWrite(...))` later in the layer."""
     if _native(qkv):
         if workspace is None:
             workspace = decode_workspace(seq_lens.numel(), k_cache.shape[1], gqa_group,
@@ -255,10 +258,13 @@ def paged_attention_decode_fused(out, qkv, k_cache, v_cache, block_tables, seq_l
                                                     seq_lens, positions, slots, cos_sin, q_w, k_w,
                                                     pm, pl, po, num_parts, part_size, gqa_group,
                                                     scale, eps, v_tail,
-                                                    tail_slot if v_tail is not None else None)
+                                                    tail_slot if v_tail is not None else None,
+                                                    write_kv)
         return out
     B, Hq = out.shape[0], out.shape[1]
     q = torch.empty_like(out)
+    if not write_kv:  # attend to the token without touching the caller's caches
+        k_cache, v_cache = k_cache.clone(), v_cache.clone()
     ref.qk_norm_rope_cache(qkv[:B], q, k_cache, v_cache, positions, slots, cos_sin, q_w, k_w, Hq,
                            k_cache.shape[1], eps, True)
     q_start = torch.arange(B + 1, dtype=torch.int32)
@@ -392,6 +398,37 @@ def silu_interleave_perm(F: int) -> torch.Tensor:
     return ((v >> 4) & 1) * F + (v >> 5) * 16 + (v & 15)
 
 
+class KvWrite(NamedTuple):
+    """The decode step's new-token K/V write as a passenger of a gate|up `dgemm` launch
+    (csrc/kernels/kv_write.h): what `paged_attention_decode_fused(write_kv=False)` left out."""
+    qkv: torch.Tensor          # [B, >= (Hq + 2 Hkv) * D] raw QKV projection rows
+    positions: torch.Tensor    # [B] int64
+    slots: torch.Tensor        # [B] int64 (-1: no write)
+    cos_sin: torch.Tensor      # [max_pos, D] fp32
+    k_w: Optional[torch.Tensor]  # [D] per-head k norm weight or None
+    k_cache: torch.Tensor
+    v_cache: torch.Tensor
+    v_tail: Optional[torch.Tensor]   # [slots, Hkv, 8, D] (the CPU reference has none)
+    tail_slot: Optional[torch.Tensor]  # [B] int32 (-1: no write)
+    num_q_heads: int
+    eps: float
+    blocks: int = 0            # > 0: at most this many rider workgroups
+
+
+def kv_rider_blocks(M: int, N: int, v, B: int, num_kv_heads: int, epi: int = EPI_SILU,
+                    kv_bf16_tail: bool = True, tp: int = 1, dense: bool = True,
+                    quantized: bool = False, cus: Optional[int] = None) -> int:
+    """Rider workgroups a dgemm launch of variant v ([M, K] x [N, K]) may carry for a decode
+    step of B sequences (kv_rider_blocks of host_contract.h); 0: none, the K/V write stays in
+    the attention kernel."""
+    v = Variant.of(v)
+    if v.family == "kgemm":
+        return 0
+    return _contract().kv_rider_blocks(M, N, epi, v.splitk, v.bn, v.ns, v.bm,
+                                       device_cus() if cus is None else cus, B, num_kv_heads,
+                                       bool(kv_bf16_tail), tp, bool(dense), bool(quantized))
+
+
 def dgemm(x: torch.Tensor, w: torch.Tensor, pro: int = PRO_PLAIN, splitk: int = 1, pf: int = 2,
           residual: Optional[torch.Tensor] = None, residual_out: Optional[torch.Tensor] = None,
           ln: Optional[torch.Tensor] = None, eps: float = 1e-6,
@@ -399,7 +436,7 @@ def dgemm(x: torch.Tensor, w: torch.Tensor, pro: int = PRO_PLAIN, splitk: int = 
           ss_in: Optional[torch.Tensor] = None, ss_out: Optional[torch.Tensor] = None,
           a_out: Optional[torch.Tensor] = None, ln_out: Optional[torch.Tensor] = None,
           bn: int = 0, ns: int = 0, inlaunch: bool = False, km: int = 0,
-          bm: int = 64, variant=None) -> torch.Tensor:
+          bm: int = 64, variant=None, kv_write: Optional[KvWrite] = None) -> torch.Tensor:
     """Fused decode GEMM (csrc/kernels/dgemm.hip): y = A @ w.T where A is produced from x by
     the prologue inside the GEMM's operand staging --
       PRO_PLAIN    A = x; with ss_in, rows of y are scaled by rsqrt(ss_in / K + eps)
@@ -429,13 +466,22 @@ def dgemm(x: torch.Tensor, w: torch.Tensor, pro: int = PRO_PLAIN, splitk: int = 
     naming it.
     km = 16 | 32 selects csrc/kernels/kgemm.hip instead: km x 32 output tiles with the K split
     over the workgroup's waves (plain prologue, store / residual epilogues, no split-K).
-    variant: a gemm_variant.Variant (or its fields as a sequence) in place of those keywords."""
+    variant: a gemm_variant.Variant (or its fields as a sequence) in place of those keywords.
+    kv_write (EPI_SILU, one K slice, ring / lds family, `kv_rider_blocks(...) > 0`): rider
+    workgroups appended to the launch write that decode step's new-token K/V rows."""
     v = Variant(splitk, pf, bn, ns, inlaunch, km, bm) if variant is None else Variant.of(variant)
     M = x.shape[0]
     N, K = w.shape
     if out is None:
         out = torch.empty(M, N // 2 if epi == EPI_SILU else N, dtype=x.dtype, device=x.device)
     if not _native(x):
+        if kv_write is not None:  # the reference writer (its cache is always complete: no tail)
+            kw = kv_write
+            nb = kw.positions.numel()
+            ref.qk_norm_rope_cache(kw.qkv[:nb], torch.empty(nb, kw.num_q_heads, 128,
+                                                            dtype=kw.qkv.dtype),
+                                   kw.k_cache, kw.v_cache, kw.positions, kw.slots, kw.cos_sin,
+                                   None, kw.k_w, kw.num_q_heads, kw.k_cache.shape[1], kw.eps, True)
         if pro == PRO_ADDNORM:
             s = (x.float() + residual.float()).to(x.dtype)
             residual_out.copy_(s)
@@ -458,11 +504,21 @@ def dgemm(x: torch.Tensor, w: torch.Tensor, pro: int = PRO_PLAIN, splitk: int = 
             out.copy_(y.to(out.dtype))
         return out
     if v.family == "kgemm":
+        if kv_write is not None:
+            raise ValueError("dgemm: kgemm variants carry no K/V riders")
         torch.ops.akap.kgemm(out, x, w, v.km, epi, eps, ss_in, ss_out, a_out, ln_out)
         return out
     ws, counters = dgemm_workspace(M, N, v, pro, x.device)
+    if kv_write is None:
+        torch.ops.akap.dgemm(out, x, w, ws, pro, v.splitk, v.pf, residual, residual_out, ln, eps,
+                             epi, ss_in, ss_out, a_out, ln_out, v.bn, v.ns, counters, v.bm)
+        return out
+    kw = kv_write
+    k_w = kw.k_w if kw.k_w is not None else kw.qkv.new_empty(0)
     torch.ops.akap.dgemm(out, x, w, ws, pro, v.splitk, v.pf, residual, residual_out, ln, eps, epi,
-                         ss_in, ss_out, a_out, ln_out, v.bn, v.ns, counters, v.bm)
+                         ss_in, ss_out, a_out, ln_out, v.bn, v.ns, counters, v.bm,
+                         [kw.qkv, kw.positions, kw.slots, kw.cos_sin, k_w, kw.k_cache, kw.v_cache,
+                          kw.v_tail, kw.tail_slot], kw.num_q_heads, kw.blocks, kw.eps)
     return out
 
 

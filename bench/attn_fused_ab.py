@@ -1,6 +1,9 @@
 """A/B in one process: decode attention on a ready q (plain kernel) vs the fused kernel that
 also does q/k RMSNorm + RoPE + the new token's K/V write from the raw QKV projection, plus
 the standalone qk_norm_rope_cache + plain attention pair.  Interleaved rounds, median.
+Also the serving form with the K/V write left to the caller (write_kv=False), and the Qwen3-0.6B
+gate|up GEMM (K 1024, N 6144, 28 rotating weights) with and without the K/V rider workgroups
+that then do that write (csrc/kernels/kv_write.h), per gate|up variant that can carry them.
 
 python bench/attn_fused_ab.py [--B 256] [--ctx 640]
 """
@@ -14,6 +17,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from aws_k8s_ansible_provisioner_amd import ops  # noqa: E402
+from aws_k8s_ansible_provisioner_amd.ops.gemm_variant import Variant  # noqa: E402
 
 
 def main():
@@ -90,9 +94,51 @@ def main():
         ops.paged_attention_decode(out, q, kc, vc, bt, lens_d, G, scale, workspace=ws,
                                    num_parts=1, part_size=4096, v_tail=vtail, tail_slot=tslot)
 
+    def fused_tail_caller():  # serving form, the new token's K/V write left to the caller
+        ops.paged_attention_decode_fused(out, qkv, kc, vc, bt, lens_d, pos_d, slots_d, cos_sin,
+                                         qw, kw, G, scale, 1e-6, workspace=ws, num_parts=1,
+                                         part_size=4096, v_tail=vtail, tail_slot=tslot,
+                                         write_kv=False)
+
     variants = {"plain attention (q ready)": plain, "plain + V tail reads": plain_tail,
                 "fused prologue attention": fused, "fused, no K/V write": fused_nowrite,
-                "fused + V tail (serving)": fused_tail, "qk_norm_rope_cache + plain": split}
+                "fused + V tail (serving)": fused_tail,
+                "fused + V tail, caller writes": fused_tail_caller,
+                "qk_norm_rope_cache + plain": split}
+    # gate|up GEMM of Qwen3-0.6B at M = B, one weight per layer so they stream from HBM
+    K_, N_, L_ = 1024, 6144, 28
+    xg = torch.randn(B, K_, dtype=torch.bfloat16, device=dev) * 0.1
+    wg = [torch.randn(N_, K_, dtype=torch.bfloat16, device=dev) * 0.05 for _ in range(L_)]
+    yg = torch.empty(B, N_ // 2, dtype=torch.bfloat16, device=dev)
+    ssg = torch.full((B,), float(K_), dtype=torch.float32, device=dev)
+    w1 = torch.randn(64, 256, dtype=torch.bfloat16, device=dev)  # one tile column, 4 k-steps
+    y1 = torch.empty(B, 32, dtype=torch.bfloat16, device=dev)
+    turn = [0]
+    gemm_keys = []
+
+    def gemm_arm(v, riders, tiles=True):
+        n = ops.kv_rider_blocks(B, N_, v, B, Hkv)
+        kvw = ops.KvWrite(qkv, pos_d, slots_d, cos_sin, kw, kc, vc, vtail, tslot, Hq, 1e-6,
+                          blocks=n) if riders else None
+
+        def run():
+            if tiles:
+                turn[0] = (turn[0] + 1) % L_
+                ops.dgemm(xg, wg[turn[0]], epi=ops.EPI_SILU, ss_in=ssg, out=yg, variant=v,
+                          kv_write=kvw)
+            else:  # the same riders behind a GEMM of 4 k-steps and one tile column
+                ops.dgemm(xg[:, :256], w1, epi=ops.EPI_SILU, out=y1, variant=v, kv_write=kvw)
+        return run
+
+    for v in (Variant(bn=128, ns=6), Variant(pf=2)):
+        n = ops.kv_rider_blocks(B, N_, v, B, Hkv)
+        if n <= 0:
+            continue
+        for label, f in ((f"gate|up s1{v.name}", gemm_arm(v, False)),
+                         (f"gate|up s1{v.name} + {n} riders", gemm_arm(v, True)),
+                         (f"{n} riders, 4-k-step tiles s1{v.name}", gemm_arm(v, True, False))):
+            variants[label] = f
+            gemm_keys.append(label)
     graphs = {}
     for k, f in variants.items():
         s = torch.cuda.Stream()
@@ -115,8 +161,9 @@ def main():
             res[k].append(e0.elapsed_time(e1) * 1000 / a.iters)
     for k, v in res.items():
         med = statistics.median(v)
-        print(f"B={B} ctx~{a.ctx} {k:30s} median {med:7.1f} us  min {min(v):7.1f} us  "
-              f"{kv_bytes / med / 1e6:5.2f} TB/s", flush=True)
+        rate = "" if k in gemm_keys else f"  {kv_bytes / med / 1e6:5.2f} TB/s"
+        print(f"B={B} ctx~{a.ctx} {k:38s} median {med:7.1f} us  min {min(v):7.1f} us  "
+              f"max {max(v):7.1f} us{rate}", flush=True)
 
 
 if __name__ == "__main__":
