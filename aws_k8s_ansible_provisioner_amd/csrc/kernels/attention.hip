@@ -8,13 +8,9 @@
 //    query rows), so after the MFMA each lane holds 8 scores of ONE query row:
 //    the online-softmax max / sum need only 2 cross-lane steps (xor 16, 32) and the
 //    score registers are directly the B operand of the next MFMA.
-//  * Rows of the two 16-token S tiles map to tokens 8*(r>>2) + 4*tile + (r&3), which
-//    makes lane group g hold tokens 8g..8g+7 contiguous -> O^T = V^T . P^T takes V^T
-//    straight from the V cache ([blk, Hkv, BS/8, D, 8]: 8-token groups, dim-major) with
-//    one 16-byte load per (dim, 8 tokens), 256 contiguous bytes per 16 lanes:
-//    no LDS transpose, no ds_bpermute.  O^T keeps the query row on the lane, so the
-//    softmax rescale is lane-local.
-//  * K operand: K cache [blk, Hkv, BS, D]; each lane loads 16 B per MFMA k-chunk.
+//  * K and V^T operands come straight from the paged caches (layout: host_contract.h, "paged
+//    KV cache layout"), 16 B per lane per MFMA k-chunk / (dim, 8 tokens): no LDS transpose,
+//    no ds_bpermute.  O^T keeps the query row on the lane, so the softmax rescale is lane-local.
 //  * Decode: grid (seq, kv_head, partition); 4 waves split a partition's 32-token
 //    chunks and combine through LDS; partitions are combined by a reduce kernel.  A wave's
 //    cache block ids sit in one VGPR (read by readlane), its K/V chunks alternate between
@@ -33,9 +29,8 @@
 
 namespace akap {
 
-constexpr int kD = 128;
-constexpr int kNC = kD / 32;  // MFMA k-chunks over the head dim
-constexpr int kND = kD / 16;  // 16-wide dim tiles of O^T
+constexpr int kNC = kKvD / 32;  // MFMA k-chunks over the head dim
+constexpr int kND = kKvD / 16;  // 16-wide dim tiles of O^T
 
 struct WaveState {
   f32x4 o[kND];
@@ -79,6 +74,27 @@ __device__ __forceinline__ auto ld_raw8(const void* base, size_t off) {
   }
 }
 
+// The hand-written fragment addresses of load_chunk_blk (decode) and of the prefill staging
+// (koff[]'s (tt, r16) form, stage_store's inverse of it) stay as text in their tuned loops; this
+// ties them to the layout of host_contract.h, so a change there breaks the build here.
+constexpr bool frags_match_layout() {
+  bool ok = v_head_base(3, 2, 1, 64) == k_head_base(3, 2, 1, 64);  // one base for both caches
+  for (int c = 0; c < 3; ++c)  // a 32-key chunk of either cache starts 32 c D past the base
+    ok = ok && k_token_offset(32 * c) == 32 * c * kKvD && v_group_offset(32 * c) == 32 * c * kKvD;
+  for (int k32 = 0; k32 < 32; ++k32)  // 16-B column dc of chunk key k32
+    for (int dc = 0; dc < 16; ++dc) {
+      const int tt = (k32 >> 2) & 1, r16 = ((k32 >> 3) << 2) | (k32 & 3);
+      const int piece = ((tt * 4 + (dc >> 2)) * 16 + r16) * 4 + (dc & 3);  // koff[] / 8
+      ok = ok && piece * 8 == k_token_offset(k32) + k_dim_offset(8 * dc) &&
+           k32 == 8 * (r16 >> 2) + 4 * tt + (r16 & 3) &&              // stage_store's key
+           k_dim_offset(8 * dc) == 512 * (dc >> 2) + 8 * (dc & 3);    // decode: + 512 cc + 8 g
+    }
+  for (int d = 0; d < kKvD; ++d)  // dim d of a V group: 8 d past the group (16-B pieces g D + d)
+    ok = ok && v_elem_offset(8, d) == v_group_offset(8) + 8 * d && v_group_offset(8) == 8 * kKvD;
+  return ok;
+}
+static_assert(frags_match_layout());
+
 // Decode form: the chunk's cache block id is given (one wave-uniform value: chunks are
 // 32-token aligned and BS is a multiple of 32, so a chunk never spans two blocks).  The
 // decode loop keeps its block ids in a VGPR (lane j = the block of the wave's j-th chunk,
@@ -93,18 +109,18 @@ __device__ __forceinline__ void load_chunk_blk(ChunkT<F8>& c, const void* __rest
   const int lane = threadIdx.x & 63;
   const int g = lane >> 4;
   const int r = lane & 15;
-  const size_t kb = ((size_t)blk * Hkv + kvh) * BS * kD;
+  const size_t kb = k_head_base(blk, Hkv, kvh, BS);
 #pragma unroll
   for (int tt = 0; tt < 2; ++tt) {
     int tok = t0 + 8 * (r >> 2) + 4 * tt + (r & 3);
     tok = min(tok, kv_len - 1);  // clamped lanes re-read a valid row (masked later)
-    const size_t kp = kb + k_swz_offset(tok % BS) + 8 * g;
+    const size_t kp = kb + k_token_offset(tok % BS) + 8 * g;
 #pragma unroll
     for (int cc = 0; cc < kNC; ++cc) c.ka[tt][cc] = ld_raw8<F8, NT>(k_cache, kp + cc * 512);
   }
   int vt = t0 + 8 * g;
   vt = min(vt, (kv_len - 1) & ~7);
-  const size_t vp = kb + ((vt % BS) >> 3) * kD * 8 + r * 8;
+  const size_t vp = kb + v_group_offset(vt % BS) + r * 8;
 #pragma unroll
   for (int n = 0; n < kND; ++n) c.vb[n] = ld_raw8<F8, NT>(v_cache, vp + 16 * n * 8);
 }
@@ -217,7 +233,7 @@ __device__ __forceinline__ void load_q(bf16x8 (&qb)[kNC], const bf16* qrow_ptr, 
 // The row arithmetic and the K / V stores are kv_write.h's (shared with the rider workgroups of
 // the gate|up GEMM launch); group_units there builds the V tail's [D][8] group image.
 
-// Fused-prologue operands loaded up front (grid decode kernel).  Every prologue load is
+// Fused-prologue operands (kv_write.h's KvRowOps) loaded up front.  Every prologue load is
 // issued BEFORE the first K/V chunk's loads, so the prologue's waits (counted vmcnt: the
 // chunk's 16 loads were issued later) leave the chunk in flight; with the loads inside the
 // prologue, their first wait drained the chunk (vmcnt is in-order) and the
@@ -225,17 +241,8 @@ __device__ __forceinline__ void load_q(bf16x8 (&qb)[kNC], const bf16* qrow_ptr, 
 // loaded whole (8 rows, valid memory) and selected afterwards: no load under a per-row
 // runtime condition (hipcc would wait on each).
 template <bool F8>
-struct ProPre {
-  bf16x8 raw, w8;
-  f32x4 c0, c1, s0, s1;
-  bf16x8 trow[8];
-  int64_t slot;
-  int tsl;
-};
-
-template <bool F8>
 __device__ __forceinline__ void prologue_loads(const AttnParams& p, int seq, int kvh,
-                                               int64_t pos, ProPre<F8>& pp) {
+                                               int64_t pos, KvRowOps& pp) {
   // Branch-free: every lane loads from a valid address (lanes past the G + 2 rows re-read row
   // G + 1's bytes; a missing norm weight / tail reads the qkv row instead), so the vmcnt
   // counts stay exact -- an exec-masked branch here made hipcc wait vmcnt(0) at the merge.
@@ -250,18 +257,18 @@ __device__ __forceinline__ void prologue_loads(const AttnParams& p, int seq, int
   const bool row_lane = rr0 < G + 2, qk_lane = rr0 <= G, v_lane = rr0 == G + 1;
   const int head = rr < G ? kvh * G + rr : (rr == G ? p.Hq + kvh : p.Hq + p.Hkv + kvh);
   const bf16* row = p.qkv + (size_t)seq * p.qkv_stride;
-  pp.raw = *reinterpret_cast<const bf16x8*>(row_lane ? row + head * kD + 8 * j : row);
+  pp.raw = *reinterpret_cast<const bf16x8*>(row_lane ? row + head * kKvD + 8 * j : row);
   const bf16* nw = rr < G ? p.q_w : p.k_w;
   pp.w8 = *reinterpret_cast<const bf16x8*>(qk_lane && nw != nullptr ? nw + 8 * j : row);
-  const float* cs = p.cos_sin + (size_t)pos * kD;
+  const float* cs = p.cos_sin + (size_t)pos * kKvD;
   const int i0 = qk_lane ? 8 * (j & 7) : 0;
   pp.c0 = *reinterpret_cast<const f32x4*>(cs + i0);
   pp.c1 = *reinterpret_cast<const f32x4*>(cs + (qk_lane ? i0 + 4 : 0));
   pp.s0 = *reinterpret_cast<const f32x4*>(cs + (qk_lane ? 64 + i0 : 0));
   pp.s1 = *reinterpret_cast<const f32x4*>(cs + (qk_lane ? 64 + i0 + 4 : 0));
   const bool tl = !F8 && p.v_tail != nullptr && v_lane;
-  const bf16* tb = tl ? p.v_tail + ((size_t)max(pp.tsl, 0) * p.Hkv + kvh) * 8 * kD + 8 * j : row;
-  const int ts = tl ? kD : 0;
+  const bf16* tb = tl ? p.v_tail + v_tail_row_offset(max(pp.tsl, 0), p.Hkv, kvh, 0) + 8 * j : row;
+  const int ts = tl ? kKvD : 0;
 #pragma unroll
   for (int i = 0; i < 8; ++i) pp.trow[i] = *reinterpret_cast<const bf16x8*>(tb + (size_t)i * ts);
 }
@@ -276,7 +283,7 @@ __device__ __forceinline__ void prologue_loads(const AttnParams& p, int seq, int
 template <bool F8>
 __device__ __forceinline__ void fused_qkv_prologue_pre(const AttnParams& p, int kvh,
                                                        bool write_kv, bf16* q_s, bool tail,
-                                                       bf16* v_img, const ProPre<F8>& pp,
+                                                       bf16* v_img, const KvRowOps& pp,
                                                        bf16* k_img) {
   const int G = p.G;
   const int rr = threadIdx.x >> 4;
@@ -293,7 +300,7 @@ __device__ __forceinline__ void fused_qkv_prologue_pre(const AttnParams& p, int 
 #pragma unroll
     for (int i = 0; i < 8; ++i) o8[i] = f2bf(x[i]);
     if (rr < G) {
-      *reinterpret_cast<bf16x8*>(q_s + rr * kD + 8 * j) = o8;
+      *reinterpret_cast<bf16x8*>(q_s + rr * kKvD + 8 * j) = o8;
     } else if (write_kv) {
       const int64_t slot = pp.slot;
       if (slot >= 0) {
@@ -304,16 +311,9 @@ __device__ __forceinline__ void fused_qkv_prologue_pre(const AttnParams& p, int 
         const int64_t blk = slot / p.BS;
         const int off = (int)(slot % p.BS);
         if (rr == G) {
-          if constexpr (F8) {
-            const size_t e = ((size_t)blk * p.Hkv + kvh) * p.BS * kD + k_swz_offset(off) +
-                             k_dim_offset(8 * j);
-            uint32_t* dst = reinterpret_cast<uint32_t*>((uint8_t*)p.k_cache + e);
-            dst[0] = f32x4_to_fp8x4((float)o8[0], (float)o8[1], (float)o8[2], (float)o8[3]);
-            dst[1] = f32x4_to_fp8x4((float)o8[4], (float)o8[5], (float)o8[6], (float)o8[7]);
-          } else {
-            if (gst) kv_store_k((bf16*)p.k_cache, p.Hkv, p.BS, kvh, slot, j, o8);
+          if (F8 || gst) kv_store_k<F8>((void*)p.k_cache, p.Hkv, p.BS, kvh, blk, off, j, o8);
+          if constexpr (!F8)
             if (tail) *reinterpret_cast<bf16x8*>(k_img + 8 * j) = o8;
-          }
         } else if (tail) {
           const int i0 = off & 7;
           bf16x8 rows[8], u[8];
@@ -325,19 +325,12 @@ __device__ __forceinline__ void fused_qkv_prologue_pre(const AttnParams& p, int 
           for (int k = 0; k < 8; ++k) *reinterpret_cast<bf16x8*>(v_img + (8 * j + k) * 8) = u[k];
           if (!gst) {
           } else if (i0 == 7) {
-            kv_store_v_group((bf16*)p.v_cache, p.Hkv, p.BS, kvh, slot, j, u);
+            kv_store_v_group((void*)p.v_cache, p.Hkv, p.BS, kvh, blk, off, j, u);
           } else {
             kv_store_v_tail_row(p.v_tail, p.Hkv, kvh, pp.tsl, i0, j, o8);
           }
         } else {
-          const size_t e = ((size_t)blk * p.Hkv + kvh) * kD * p.BS + (off >> 3) * kD * 8 + (off & 7);
-#pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            if constexpr (F8)
-              ((uint8_t*)p.v_cache)[e + (size_t)(8 * j + i) * 8] = f32_to_fp8((float)o8[i]);
-            else
-              ((bf16*)p.v_cache)[e + (size_t)(8 * j + i) * 8] = o8[i];
-          }
+          kv_store_v_token<F8>((void*)p.v_cache, p.Hkv, p.BS, kvh, blk, off, j, o8);
         }
       }
     }
@@ -359,23 +352,25 @@ __device__ __forceinline__ void fused_qkv_prologue_pre(const AttnParams& p, int 
 // LDS images), and the next kernel sees them after the launch boundary.
 template <bool F8>
 __device__ __forceinline__ void deferred_kv_stores(const AttnParams& p, int kvh,
-                                                   const ProPre<F8>& pp, const bf16* k_img,
+                                                   const KvRowOps& pp, const bf16* k_img,
                                                    const bf16* v_img) {
   const int rr = threadIdx.x >> 4;
   const int j = threadIdx.x & 15;
   const int G = p.G;
   if (rr != G && rr != G + 1) return;
+  const int64_t blk = pp.slot / p.BS;
+  const int off = (int)(pp.slot % p.BS);
   if (rr == G) {
-    kv_store_k((bf16*)p.k_cache, p.Hkv, p.BS, kvh, pp.slot, j,
+    kv_store_k((void*)p.k_cache, p.Hkv, p.BS, kvh, blk, off, j,
                *reinterpret_cast<const bf16x8*>(k_img + 8 * j));
     return;
   }
-  const int i0 = (int)(pp.slot % p.BS) & 7;
+  const int i0 = off & 7;
   if (i0 == 7) {  // the group is complete: its [D][8] image goes to the cache
     bf16x8 u[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) u[k] = *reinterpret_cast<const bf16x8*>(v_img + (8 * j + k) * 8);
-    kv_store_v_group((bf16*)p.v_cache, p.Hkv, p.BS, kvh, pp.slot, j, u);
+    kv_store_v_group((void*)p.v_cache, p.Hkv, p.BS, kvh, blk, off, j, u);
   } else {  // the token's row (dims 8j..8j+7) goes to the sequence's V tail
     bf16x8 o8;
 #pragma unroll
@@ -392,7 +387,7 @@ constexpr bool kDecodeNT = true;
 //  head: what the item needs before its first K/V byte can be requested -- the sequence's
 //    length, the cache block ids of the wave's chunks (lane j: chunk pstart + 32 w + 128 j,
 //    read later with readlane: an SGPR, no memory instruction in the chunk loop), in the
-//    fused form the prologue's operands (ProPre, issued ahead of the chunk), then the wave's
+//    fused form the prologue's operands (KvRowOps, issued ahead of the chunk), then the wave's
 //    first chunk in flight.  The block-id load does not wait for the length (the index is
 //    clamped into the block-table row instead of guarded by it), so the chain before the
 //    first K/V load is two round trips.
@@ -412,8 +407,8 @@ __device__ __forceinline__ void decode_item(const AttnParams& p, int seq, int kv
   const int btr =
       p.block_tables[(size_t)seq * p.bt_stride + min((t0 + 128 * lane) / p.BS, p.bt_stride - 1)];
   const int kv_len = p.seq_lens[seq];
-  ProPre<F8> pp;
-  if constexpr (FUSED) {  // fused-prologue operands: issued ahead of the chunk (see ProPre)
+  KvRowOps pp;
+  if constexpr (FUSED) {  // fused-prologue operands: issued ahead of the chunk (see prologue_loads)
     const int64_t pos = p.positions[seq];
     pp.slot = p.slots[seq];
     pp.tsl = (!F8 && p.v_tail != nullptr) ? p.tail_slot[seq] : -1;
@@ -433,17 +428,17 @@ __device__ __forceinline__ void decode_item(const AttnParams& p, int seq, int kv
   const int qr = lane & 15;
   const bool valid = qr < G && kv_len > 0;
   const int q_tok = p.q_start ? p.q_start[seq] : seq;
-  const bf16* qptr = FUSED ? nullptr : p.q + ((size_t)q_tok * p.Hq + kvh * G + qr) * kD;
+  const bf16* qptr = FUSED ? nullptr : p.q + ((size_t)q_tok * p.Hq + kvh * G + qr) * kKvD;
 
   // combine buffer sized by G (dynamic LDS: 4 x G x (D+4) floats + stats), so small G
   // keeps LDS from limiting occupancy (G=2: ~4 KiB instead of 34 KiB)
-  float* o_s = dyn_lds;                       // [4][G][kD + 4]
-  float* m_s = dyn_lds + 4 * G * (kD + 4);    // [4][G]
+  float* o_s = dyn_lds;                       // [4][G][kKvD + 4]
+  float* m_s = dyn_lds + 4 * G * (kKvD + 4);    // [4][G]
   float* l_s = m_s + 4 * G;                   // [4][G]
-#define OS(w_, r_, d_) o_s[((w_) * G + (r_)) * (kD + 4) + (d_)]
-  bf16* q_s = reinterpret_cast<bf16*>(l_s + 4 * G);  // [G][kD] (fused only)
-  bf16* v_img = q_s + (FUSED ? G * kD : 0);          // [kD][8] V tail group image
-  bf16* k_img = v_img + kD * 8;                      // [kD] new token's K (fused + V tail)
+#define OS(w_, r_, d_) o_s[((w_) * G + (r_)) * (kKvD + 4) + (d_)]
+  bf16* q_s = reinterpret_cast<bf16*>(l_s + 4 * G);  // [G][kKvD] (fused only)
+  bf16* v_img = q_s + (FUSED ? G * kKvD : 0);          // [kKvD][8] V tail group image
+  bf16* k_img = v_img + kKvD * 8;                      // [kKvD] new token's K (fused + V tail)
   const int limit = kv_len - 1;
   const bool writes_kv = kv_len > 0 && pstart <= kv_len - 1 && kv_len - 1 < pend;
   // V tail: the sequence's last 8-token group (first token gstart) is read from an LDS image
@@ -472,11 +467,11 @@ __device__ __forceinline__ void decode_item(const AttnParams& p, int seq, int kv
     if (threadIdx.x < 16) {
       const int j = threadIdx.x;
       const int cnt = kv_len - gstart;
-      const bf16* tb = p.v_tail + ((size_t)tsl * p.Hkv + kvh) * 8 * kD + 8 * j;
+      const bf16* tb = p.v_tail + v_tail_row_offset(tsl, p.Hkv, kvh, 0) + 8 * j;
       bf16x8 rows[8], u[8];
 #pragma unroll
       for (int i = 0; i < 8; ++i)
-        rows[i] = i < cnt ? *reinterpret_cast<const bf16x8*>(tb + (size_t)i * kD)
+        rows[i] = i < cnt ? *reinterpret_cast<const bf16x8*>(tb + (size_t)i * kKvD)
                           : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
       group_units(rows, u);
 #pragma unroll
@@ -491,7 +486,7 @@ __device__ __forceinline__ void decode_item(const AttnParams& p, int seq, int kv
     if constexpr (FUSED) {
 #pragma unroll
       for (int c = 0; c < kNC; ++c)
-        qb[c] = valid ? *reinterpret_cast<const bf16x8*>(q_s + qr * kD + 32 * c + 8 * g)
+        qb[c] = valid ? *reinterpret_cast<const bf16x8*>(q_s + qr * kKvD + 32 * c + 8 * g)
                       : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
     } else {
       load_q(qb, qptr, valid);
@@ -561,14 +556,14 @@ __device__ __forceinline__ void decode_item(const AttnParams& p, int seq, int kv
     }
     const float inv = L > 0.f ? 1.f / L : 0.f;
     if (p.num_parts == 1) {
-      bf16* op = p.out + ((size_t)q_tok * p.Hq + kvh * G + row) * kD + d0;
+      bf16* op = p.out + ((size_t)q_tok * p.Hq + kvh * G + row) * kKvD + d0;
       bf16x8 o8;
 #pragma unroll
       for (int j = 0; j < 8; ++j) o8[j] = f2bf(acc[j] * inv);
       *reinterpret_cast<bf16x8*>(op) = o8;
     } else {
       const size_t pidx = ((size_t)(seq * p.Hkv + kvh) * p.num_parts + part) * G + row;
-      float* po = p.part_o + pidx * kD + d0;
+      float* po = p.part_o + pidx * kKvD + d0;
 #pragma unroll
       for (int j = 0; j < 8; ++j) po[j] = acc[j] * inv;
       if ((threadIdx.x & 15) == 0) {
@@ -670,8 +665,8 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void paged_attn_prefill_fa_kernel(
   static_assert(!STAG || (NW == 8 && GL), "the ping-pong pairs waves w and w + 4");
   // [buf][K | V][64 keys * 128 dims] bf16 = 64 KiB (96 KiB with STAG) + the block ids of the
   // first kFaBtCache 32-key chunks; ONE __shared__ object (a second one makes hipcc drain vmcnt)
-  __shared__ __attribute__((aligned(16))) bf16 lds[NBUF * 2 * kFaKeys * kD + 2 * kFaBtCache];
-  int* bt_s = reinterpret_cast<int*>(lds + NBUF * 2 * kFaKeys * kD);
+  __shared__ __attribute__((aligned(16))) bf16 lds[NBUF * 2 * kFaKeys * kKvD + 2 * kFaBtCache];
+  int* bt_s = reinterpret_cast<int*>(lds + NBUF * 2 * kFaKeys * kKvD);
   // One flat grid of (tile, kv head) items, kv head innermost, dispatched back to front: the
   // host map is sorted by ascending causal work (scheduler.cpp), so every head of the longest
   // tiles starts first and the grid's tail is made of the shortest ones (longest-first over
@@ -711,10 +706,10 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void paged_attn_prefill_fa_kernel(
     // in the same lane, so the rotation is lane-local.  Same arithmetic as rope_cache.hip
     // qk_tok.
     const int tok = q0 + (valid ? pos : 0);
-    const bf16* src = p.qkv + (size_t)tok * p.qkv_stride + (size_t)(kvh * G + hig) * kD + 8 * h;
+    const bf16* src = p.qkv + (size_t)tok * p.qkv_stride + (size_t)(kvh * G + hig) * kKvD + 8 * h;
     // rotary position = the token's key index ctx0 + pos -- the invariant the causal limit
     // above already relies on (positions[tok] holds the same value): no dependent load
-    const float* cs = p.cos_sin + (size_t)(valid ? ctx0 + pos : 0) * kD + 8 * h;
+    const float* cs = p.cos_sin + (size_t)(valid ? ctx0 + pos : 0) * kKvD + 8 * h;
     // every operand load issued up front, unconditionally (one round trip; without a q norm
     // the weight loads read valid rotary-table bytes and are ignored)
     const bool qn = p.q_w != nullptr;
@@ -744,7 +739,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void paged_attn_prefill_fa_kernel(
     for (int s8 = 0; s8 < 8; ++s8)
 #pragma unroll
       for (int j = 0; j < 8; ++j) ss += bf2f(raw[s8][j]) * bf2f(raw[s8][j]);
-    const float inv = rsqrtf(xor32_sum(ss) / (float)kD + p.eps);
+    const float inv = rsqrtf(xor32_sum(ss) / (float)kKvD + p.eps);
     // normed value of dim (s8, j), bf16-rounded like the standalone kernel (raw without a norm)
     auto xn = [&](int s8, int j) {
       const float v = bf2f(raw[s8][j]);
@@ -765,7 +760,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void paged_attn_prefill_fa_kernel(
       qf[s8 + 4] = valid ? hi : z;
     }
   } else {
-    const bf16* qrow = p.q + ((size_t)(q0 + (valid ? pos : 0)) * p.Hq + kvh * G + hig) * kD;
+    const bf16* qrow = p.q + ((size_t)(q0 + (valid ? pos : 0)) * p.Hq + kvh * G + hig) * kKvD;
 #pragma unroll
     for (int s8 = 0; s8 < 8; ++s8)
       qf[s8] = valid ? *reinterpret_cast<const bf16x8*>(qrow + 16 * s8 + 8 * h)
@@ -801,15 +796,15 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void paged_attn_prefill_fa_kernel(
       const int c = pc >> 9;           // 32-key chunk of the tile
       const int within = pc & 511;
       const int off = (min(t * 2 + c, last_chunk) * 32) % BS;
-      const size_t base = ((size_t)blk[i] * p.Hkv + kvh) * BS * kD + (size_t)off * kD;
+      const size_t base = AKAP_K_HEAD_BASE(blk[i], p.Hkv, kvh, BS) + (size_t)off * kKvD;
       // fp8 caches: 8-byte loads widened to bf16 here, so the LDS images are the same
       kst[i] = ld_kv8<F8, false>(p.k_cache, base + within * 8);
       vst[i] = ld_kv8<F8, false>(p.v_cache, base + within * 8);
     }
   };
   auto stage_store = [&](int buf) {
-    bf16* kl = lds + (size_t)buf * 2 * kFaKeys * kD;
-    bf16* vl = kl + kFaKeys * kD;
+    bf16* kl = lds + (size_t)buf * 2 * kFaKeys * kKvD;
+    bf16* vl = kl + kFaKeys * kKvD;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int pc = tid + 256 * i;
@@ -822,8 +817,8 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void paged_attn_prefill_fa_kernel(
       const int tt = within >> 8;
       const int key = 32 * c + 8 * (r16 >> 2) + 4 * tt + (r16 & 3);
       const int dc = 4 * cc + q4;  // 16-B column of the 256-B key row
-      *reinterpret_cast<bf16x8*>(kl + key * kD + ((dc ^ (key & 15)) * 8)) = kst[i];
-      *reinterpret_cast<bf16x8*>(vl + c * 32 * kD + within * 8) = vst[i];
+      *reinterpret_cast<bf16x8*>(kl + key * kKvD + ((dc ^ (key & 15)) * 8)) = kst[i];
+      *reinterpret_cast<bf16x8*>(vl + c * 32 * kKvD + within * 8) = vst[i];
     }
   };
 
@@ -855,11 +850,11 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void paged_attn_prefill_fa_kernel(
       (const __attribute__((address_space(4))) int*)bt;
   auto blk_of = [&](int t) { return bt_c[chunk_of(t) * 32 / BS]; };
   auto stage_glds = [&](int t, int buf, int blk) {
-    bf16* kl = lds + (size_t)buf * 2 * kFaKeys * kD;
-    bf16* vl = kl + kFaKeys * kD;
+    bf16* kl = lds + (size_t)buf * 2 * kFaKeys * kKvD;
+    bf16* vl = kl + kFaKeys * kKvD;
     const int chunk = chunk_of(t);
     const size_t base =
-        ((size_t)blk * p.Hkv + kvh) * BS * kD + (size_t)((chunk * 32) % BS) * kD;
+        AKAP_K_HEAD_BASE(blk, p.Hkv, kvh, BS) + (size_t)((chunk * 32) % BS) * kKvD;
     const bf16* kb = static_cast<const bf16*>(p.k_cache) + base;
     const bf16* vb = static_cast<const bf16*>(p.v_cache) + base;
 #pragma unroll
@@ -901,7 +896,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void paged_attn_prefill_fa_kernel(
 #pragma unroll
         for (int j = 0; j < 16; ++j) oacc[i][j] *= alpha_d;
     }
-    const bf16* vlp = lds + (size_t)(tp % NBUF) * 2 * kFaKeys * kD + kFaKeys * kD;
+    const bf16* vlp = lds + (size_t)(tp % NBUF) * 2 * kFaKeys * kKvD + kFaKeys * kKvD;
 #pragma unroll
     for (int k = 0; k < 2; ++k)
 #pragma unroll
@@ -909,7 +904,8 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void paged_attn_prefill_fa_kernel(
         bf16x8 v4[4];
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt)
-          v4[dt] = *reinterpret_cast<const bf16x8*>(vlp + ((4 * k + 2 * s2 + h) * kD + 32 * dt + r) * 8);
+          v4[dt] = *reinterpret_cast<const bf16x8*>(
+              vlp + ((4 * k + 2 * s2 + h) * kKvD + 32 * dt + r) * 8);
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt)
           oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(v4[dt], pd[k][s2], oacc[dt], 0, 0, 0);
@@ -941,8 +937,8 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void paged_attn_prefill_fa_kernel(
     if (late && pend) deferred_pv(t - 1);
     const int key0 = t * kFaKeys;
     if (wave_active && key0 <= w_limit) {
-      const bf16* kl = lds + (size_t)buf * 2 * kFaKeys * kD;
-      const bf16* vl = kl + kFaKeys * kD;
+      const bf16* kl = lds + (size_t)buf * 2 * kFaKeys * kKvD;
+      const bf16* vl = kl + kFaKeys * kKvD;
       // S^T = K . Q^T for the two 32-key sub-tiles (interleaved: independent chains)
       f32x16 sacc[2];
 #pragma unroll
@@ -958,7 +954,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void paged_attn_prefill_fa_kernel(
         for (int k = 0; k < 2; ++k) {
           const int key = 32 * k + fa_row_key(r);
           kf[s8][k] = *reinterpret_cast<const bf16x8*>(
-              kl + key * kD + (((2 * s8 + h) ^ (key & 15)) * 8));
+              kl + key * kKvD + (((2 * s8 + h) ^ (key & 15)) * 8));
         }
 #pragma unroll
       for (int s8 = 0; s8 < 8; ++s8)
@@ -976,7 +972,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void paged_attn_prefill_fa_kernel(
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt)
               vf[k][s2][dt] = *reinterpret_cast<const bf16x8*>(
-                  vl + ((4 * k + 2 * s2 + h) * kD + 32 * dt + r) * 8);
+                  vl + ((4 * k + 2 * s2 + h) * kKvD + 32 * dt + r) * 8);
       }
       // causal mask (wave-uniform branch: only tiles that cross this wave's diagonal pay for
       // it) and the running max on the raw scores -- the log2-domain scale is positive, so
@@ -1076,7 +1072,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void paged_attn_prefill_fa_kernel(
   // 16 kp + 8..15 of the same row: one 16-B store per pair instead of two 8-B stores (the
   // epilogue is store-issue bound: 18 us of 117 at 32 x 512, profiles/r2_pmc_prefill_v2.md)
   const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
-  bf16* orow = p.out + ((size_t)(q0 + (valid ? pos : 0)) * p.Hq + kvh * G + hig) * kD;
+  bf16* orow = p.out + ((size_t)(q0 + (valid ? pos : 0)) * p.Hq + kvh * G + hig) * kKvD;
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
@@ -1115,7 +1111,7 @@ __global__ __launch_bounds__(256) void paged_attn_reduce_kernel(AttnParams p) {
     const size_t idx = base + (size_t)q * G;
     const float f = exp2f(p.part_m[idx] - M) * p.part_l[idx];
     L += f;
-    const f32x4* po = reinterpret_cast<const f32x4*>(p.part_o + idx * kD + d0);
+    const f32x4* po = reinterpret_cast<const f32x4*>(p.part_o + idx * kKvD + d0);
     f32x4 a = po[0], b = po[1];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -1125,7 +1121,7 @@ __global__ __launch_bounds__(256) void paged_attn_reduce_kernel(AttnParams p) {
   }
   const float inv = L > 0.f ? 1.f / L : 0.f;
   const int q_tok = p.q_start ? p.q_start[seq] : seq;
-  bf16* op = p.out + ((size_t)q_tok * p.Hq + kvh * G + row) * kD + d0;
+  bf16* op = p.out + ((size_t)q_tok * p.Hq + kvh * G + row) * kKvD + d0;
   bf16x8 o8;
 #pragma unroll
   for (int j = 0; j < 8; ++j) o8[j] = f2bf(acc[j] * inv);
@@ -1164,10 +1160,10 @@ void launch_paged_attn_decode(const AttnParams& p, int num_seqs, hipStream_t s) 
   if ((p.flags & kAttnCallerWritesKv) && (p.kv_fp8 || p.v_tail == nullptr || p.qkv == nullptr))
     throw std::invalid_argument(
         "paged_attn_decode: kAttnCallerWritesKv needs the fused form, bf16 caches and a V tail");
-  const size_t smem = (size_t)(4 * p.G * (kD + 4) + 8 * p.G) * sizeof(float) +
-                      (p.qkv ? (size_t)p.G * kD * sizeof(bf16) : 0) +
-                      (p.v_tail ? (size_t)kD * 8 * sizeof(bf16) : 0) +
-                      (p.qkv && p.v_tail ? (size_t)kD * sizeof(bf16) : 0);
+  const size_t smem = (size_t)(4 * p.G * (kKvD + 4) + 8 * p.G) * sizeof(float) +
+                      (p.qkv ? (size_t)p.G * kKvD * sizeof(bf16) : 0) +
+                      (p.v_tail ? (size_t)kKvD * 8 * sizeof(bf16) : 0) +
+                      (p.qkv && p.v_tail ? (size_t)kKvD * sizeof(bf16) : 0);
   const dim3 grid(num_seqs, p.Hkv, p.num_parts);
   static const int defer_kv = [] {  // AKAP_DECODE_DEFER_KV=0: stores in the prologue (A/B)
     const char* e = std::getenv("AKAP_DECODE_DEFER_KV");

@@ -5,6 +5,8 @@
 // checks, the tuner's enumeration, the engine's workspace sizing and the tests ask one function.
 #pragma once
 
+#include <stddef.h>
+
 namespace akap {
 
 // Ints per in-launch ticket counter: each counter on its own 128-B L2 line.  Atomics (and the
@@ -274,6 +276,56 @@ inline DGemmContract dgemm_contract(int M, int N, int K, int pro, int epi, int s
                                kCtrStride;
   }
   return c;
+}
+
+// ---- paged KV cache layout ----
+// The one definition of where a (block, kv head, token, dim) element of the paged caches lives;
+// every kernel, ops.cpp and Python (`_runtime.contract`) take it from here.  Offsets are in
+// elements (bf16, or bytes of an fp8 cache).  Chosen so the attention kernels issue 16-byte
+// MFMA-operand loads with no transpose, 1 KiB contiguous per load instruction:
+//   K cache: [num_blocks, Hkv, BS, D] shape, BS % 32 == 0.  Within one (block, kv head) each
+//            32-token chunk is stored as [tile tt (2)][k-step cc (4)][row r (16)][32 dims]: the
+//            exact operand order of the attention kernels' S^T = K.Q^T MFMA tiles, whose row r
+//            of tile tt is chunk token 8*(r>>2) + 4*tt + (r&3).  That row order makes a lane
+//            group hold 8 contiguous tokens, which is what lets V^T come straight from:
+//   V cache: [num_blocks, Hkv, BS/8, D, 8] (8-token groups, dim-major inside a group): the
+//            attention kernel's V^T operand (one dim, 8 consecutive tokens) is one 16-byte
+//            load, and a token's 128 dims land in 16-byte-strided slots of one 2 KiB group
+//            (4x fewer cache lines touched per written token than [D][BS]).
+//   V tail:  [tail slots, Hkv, 8, D] bf16, token-major: a sequence's still-partial last V
+//            group, so decode steps write no partial cache lines.
+constexpr int kKvD = 128, kKvChunk = 32;       // head dim; tokens per K chunk
+constexpr int kKvGroup = 8, kVTailRows = 8;    // tokens per V group; V-tail rows per kv head
+
+// First element of a (block, kv head) in the K and in the V cache, the 8-token V group of token
+// `off` within it, and row 0 of a (tail slot, kv head) of the V tail.  These four also exist as
+// macros: a kernel whose tuned code changes when the arithmetic arrives through an inlined
+// function (rope_cache.hip, the prefill staging of attention.hip) expands the same text in place.
+#define AKAP_K_HEAD_BASE(blk, Hkv, h, BS) (((size_t)(blk) * (Hkv) + (h)) * (BS) * akap::kKvD)
+#define AKAP_V_HEAD_BASE(blk, Hkv, h, BS) (((size_t)(blk) * (Hkv) + (h)) * akap::kKvD * (BS))
+#define AKAP_V_GROUP_OFFSET(off) (((off) >> 3) * akap::kKvD * akap::kKvGroup)
+#define AKAP_V_TAIL_BASE(tsl, Hkv, h) \
+  (((size_t)(tsl) * (Hkv) + (h)) * akap::kVTailRows * akap::kKvD)
+constexpr size_t k_head_base(size_t blk, int Hkv, int h, int BS) {
+  return AKAP_K_HEAD_BASE(blk, Hkv, h, BS);
+}
+constexpr size_t v_head_base(size_t blk, int Hkv, int h, int BS) {
+  return AKAP_V_HEAD_BASE(blk, Hkv, h, BS);
+}
+// K: (token `off` of the block, dim 0) within the block-head; dim d is k_dim_offset(d) further
+constexpr int k_token_offset(int off) {
+  const int o = off & (kKvChunk - 1);
+  const int tt = (o >> 2) & 1;
+  const int r = ((o >> 3) << 2) | (o & 3);
+  return (off >> 5) * kKvChunk * kKvD + tt * 16 * kKvD + r * 32;
+}
+constexpr int k_dim_offset(int d) { return (d >> 5) * 512 + (d & 31); }
+// V: the 8-token group of token `off`, and its element (token off, dim d), within the block-head
+constexpr int v_group_offset(int off) { return AKAP_V_GROUP_OFFSET(off); }
+constexpr int v_elem_offset(int off, int d) { return v_group_offset(off) + d * 8 + (off & 7); }
+// V tail: dim 0 of row `row` (token row of the partial group) of a (tail slot, kv head)
+constexpr size_t v_tail_row_offset(size_t tsl, int Hkv, int h, int row) {
+  return AKAP_V_TAIL_BASE(tsl, Hkv, h) + (size_t)row * kKvD;
 }
 
 // ---- K/V rider workgroups of the gate|up decode GEMM launch (kv_write.h) ----

@@ -15,8 +15,6 @@
 
 namespace akap {
 
-constexpr int kKvD = 128;  // head dim of the paged caches
-
 // 16 lanes (j = dims [8j, 8j+8)) hold an 8-token group token-major (rows[i] = token i) and
 // turn it into the cache's [D][8] group image (dim-major, 16 B per dim): u[k] = dim 8j + k
 __device__ __forceinline__ void group_units(const bf16x8 (&rows)[8], bf16x8 (&u)[8]) {
@@ -51,31 +49,74 @@ __device__ __forceinline__ void head_norm_rope(float (&x)[8], bool norm, const b
   }
 }
 
-// the K row of token `slot`, dims [8j, 8j+8): one 16-B store in k_swz_offset / k_dim_offset order
-__device__ __forceinline__ void kv_store_k(bf16* k_cache, int Hkv, int BS, int kvh, int64_t slot,
-                                           int j, const bf16x8& k8) {
-  const int64_t blk = slot / BS;
-  const int off = (int)(slot % BS);
-  const size_t e = ((size_t)blk * Hkv + kvh) * BS * kKvD + k_swz_offset(off) + k_dim_offset(8 * j);
-  *reinterpret_cast<bf16x8*>(k_cache + e) = k8;
+// 8 consecutive cache elements at element `e` <- bf16x8: one 16-B store, or (fp8 cache) the pack
+// of the bf16-rounded values and one 8-B store.  The counterpart of ld_kv8.
+template <bool F8>
+__device__ __forceinline__ void st_kv8(void* cache, size_t e, const bf16x8& v) {
+  if constexpr (F8) {
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    u32x2 w;
+    w[0] = f32x4_to_fp8x4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
+    w[1] = f32x4_to_fp8x4((float)v[4], (float)v[5], (float)v[6], (float)v[7]);
+    *reinterpret_cast<u32x2*>(reinterpret_cast<uint8_t*>(cache) + e) = w;
+  } else {
+    *reinterpret_cast<bf16x8*>(reinterpret_cast<bf16*>(cache) + e) = v;
+  }
+}
+template <bool F8>
+__device__ __forceinline__ void st_kv1(void* cache, size_t e, bf16 v) {
+  if constexpr (F8) reinterpret_cast<uint8_t*>(cache)[e] = f32_to_fp8((float)v);
+  else reinterpret_cast<bf16*>(cache)[e] = v;
+}
+
+// The V stores here and in rope_cache.hip add the element step to the group themselves; it is the
+// layout's: dim d of token off sits 8 d + off % 8 past AKAP_V_GROUP_OFFSET(off).
+constexpr bool v_steps_match_layout() {
+  bool ok = true;
+  for (int i = 0; i < 64 * kKvD; ++i)  // (off, d) = (i / D, i % D)
+    ok = ok && v_elem_offset(i / kKvD, i % kKvD) ==
+                   AKAP_V_GROUP_OFFSET(i / kKvD) + (i % kKvD) * 8 + ((i / kKvD) & 7);
+  return ok;
+}
+static_assert(v_steps_match_layout());
+
+// The stores take a cache slot as (blk, off) = (slot / BS, slot % BS): 64-bit divisions, done
+// once by a caller with several stores; the bases in their macro form (host_contract.h), which
+// keeps the callers' tuned code.  The K row of token off of block blk, dims [8j, 8j+8):
+template <bool F8 = false>
+__device__ __forceinline__ void kv_store_k(void* k_cache, int Hkv, int BS, int kvh, int64_t blk,
+                                           int off, int j, const bf16x8& k8) {
+  st_kv8<F8>(k_cache,
+             AKAP_K_HEAD_BASE(blk, Hkv, kvh, BS) + k_token_offset(off) + k_dim_offset(8 * j), k8);
 }
 
 // a still-partial V group: the token's row (dims [8j, 8j+8)) goes to row i0 of the sequence's tail
 __device__ __forceinline__ void kv_store_v_tail_row(bf16* v_tail, int Hkv, int kvh, int tsl,
                                                     int i0, int j, const bf16x8& v8) {
-  bf16* tb = v_tail + ((size_t)tsl * Hkv + kvh) * 8 * kKvD + 8 * j;
+  // row 0, then the row step (rows are kKvD apart): as one sum the rider GEMMs take a VGPR more
+  bf16* tb = v_tail + AKAP_V_TAIL_BASE(tsl, Hkv, kvh) + 8 * j;
   *reinterpret_cast<bf16x8*>(tb + (size_t)i0 * kKvD) = v8;
 }
 
 // a completed V group: its [D][8] image (u[k] = dim 8j + k, 8 tokens) goes to the cache
-__device__ __forceinline__ void kv_store_v_group(bf16* v_cache, int Hkv, int BS, int kvh,
-                                                 int64_t slot, int j, const bf16x8 (&u)[8]) {
-  const int64_t blk = slot / BS;
-  const int off = (int)(slot % BS);
-  bf16* e = v_cache + ((size_t)blk * Hkv + kvh) * kKvD * BS + (off >> 3) * kKvD * 8 +
-            (size_t)(8 * j) * 8;
+template <bool F8 = false>
+__device__ __forceinline__ void kv_store_v_group(void* v_cache, int Hkv, int BS, int kvh,
+                                                 int64_t blk, int off, int j,
+                                                 const bf16x8 (&u)[8]) {
+  const size_t e =
+      AKAP_V_HEAD_BASE(blk, Hkv, kvh, BS) + AKAP_V_GROUP_OFFSET(off) + (size_t)(8 * j) * 8;
 #pragma unroll
-  for (int k = 0; k < 8; ++k) *reinterpret_cast<bf16x8*>(e + 8 * k) = u[k];
+  for (int k = 0; k < 8; ++k) st_kv8<F8>(v_cache, e + 8 * k, u[k]);
+}
+
+// one token of a V group: its dims [8j, 8j+8) go to the group's token column, 8 elements apart
+template <bool F8 = false>
+__device__ __forceinline__ void kv_store_v_token(void* v_cache, int Hkv, int BS, int kvh,
+                                                 int64_t blk, int off, int j, const bf16x8& v8) {
+  const size_t e = AKAP_V_HEAD_BASE(blk, Hkv, kvh, BS) + AKAP_V_GROUP_OFFSET(off) + (off & 7) +
+                   (size_t)(8 * j) * 8;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) st_kv1<F8>(v_cache, e + 8 * k, v8[k]);
 }
 
 // Operands of one (sequence, kv head, K | V) row, loaded up front by 16 lanes.
@@ -93,6 +134,8 @@ struct KvRowOps {
 __device__ __forceinline__ void kv_write_row(const KvWriteArgs& a, int kvh, bool is_v, bool live,
                                              int j, const KvRowOps& r) {
   const bool wr = live && r.slot >= 0 && r.tsl >= 0;
+  // slot / BS and slot % BS stay inside the K and the V branch: hoisted above them the rider GEMMs
+  // are ~350 lines shorter but take 3 to 8 VGPRs more (profiles/kv_layout_refactor.md)
   bf16* kc = static_cast<bf16*>(a.k_cache);
   bf16* vc = static_cast<bf16*>(a.v_cache);
   bf16* vt = static_cast<bf16*>(a.v_tail);
@@ -104,7 +147,7 @@ __device__ __forceinline__ void kv_write_row(const KvWriteArgs& a, int kvh, bool
     bf16x8 o8;
 #pragma unroll
     for (int i = 0; i < 8; ++i) o8[i] = f2bf(x[i]);
-    if (wr) kv_store_k(kc, a.Hkv, a.BS, kvh, r.slot, j, o8);
+    if (wr) kv_store_k(kc, a.Hkv, a.BS, kvh, r.slot / a.BS, (int)(r.slot % a.BS), j, o8);
   } else if (wr) {
     const int i0 = (int)(r.slot % a.BS) & 7;
     if (i0 == 7) {  // rows 0..6 from the tail, row 7 = the new token
@@ -113,7 +156,7 @@ __device__ __forceinline__ void kv_write_row(const KvWriteArgs& a, int kvh, bool
       for (int i = 0; i < 7; ++i) rows[i] = r.trow[i];
       rows[7] = r.raw;
       group_units(rows, u);
-      kv_store_v_group(vc, a.Hkv, a.BS, kvh, r.slot, j, u);
+      kv_store_v_group(vc, a.Hkv, a.BS, kvh, r.slot / a.BS, (int)(r.slot % a.BS), j, u);
     } else {
       kv_store_v_tail_row(vt, a.Hkv, kvh, r.tsl, i0, j, r.raw);
     }
@@ -169,7 +212,7 @@ __device__ __forceinline__ void kv_rider_block(const KvWriteArgs& a, int rider, 
       r[u].s0 = *reinterpret_cast<const f32x4*>(cs + 64 + i0);
       r[u].s1 = *reinterpret_cast<const f32x4*>(cs + 64 + i0 + 4);
       const bf16* tb =
-          is_v ? vt + ((size_t)max(r[u].tsl, 0) * a.Hkv + kvh[u]) * 8 * kKvD + 8 * j : row;
+          is_v ? vt + AKAP_V_TAIL_BASE(max(r[u].tsl, 0), a.Hkv, kvh[u]) + 8 * j : row;
       const int ts = is_v ? kKvD : 0;
 #pragma unroll
       for (int i = 0; i < 8; ++i)

@@ -6,18 +6,17 @@
 // launch: q/k heads and V spans are distinct workgroup roles of the same grid.  cos/sin come
 // from a host-precomputed fp32 table [max_pos, D] (cos | sin), no on-device trig.
 //
-// Paged cache layouts (MI355X-first, chosen so the attention kernels can issue
-// 16-byte MFMA-operand loads with no transpose, 1 KiB contiguous per load instruction):
-//   K cache: [num_blocks, Hkv, BS, D] shape, MFMA-fragment order inside each 32-token
-//            chunk (k_swz_offset in common.h)
-//   V cache: [num_blocks, Hkv, BS/8, D, 8] (8-token groups, dim-major inside a group):
-//            the attention kernel's V^T operand (one dim, 8 consecutive tokens) is one
-//            16-byte load, and a token's 128 dims land in 16-byte-strided slots of one
-//            2 KiB group (4x fewer cache lines touched per written token than [D][BS]).
+// The paged cache layouts are host_contract.h's ("paged KV cache layout").
 #include "common.h"
 #include "kernels.h"
+#include "kv_write.h"
 
 namespace akap {
+
+// qk_tok, v_span and v_item write their addresses out like kv_write.h's stores (macro bases, the
+// V element step checked there): through those stores or the layout's inlined functions
+// qk_norm_rope_cache_kernel compiles to other code, which measured slower
+// (profiles/kv_layout_refactor.md, "Timing").
 
 // q/k role: 16 lanes own one token; lane i holds the 8 contiguous dims [8i, 8i+8) of a head
 // row (one 16-byte load / store), its rotate-half partner dims live in lane i ^ 8 and are
@@ -53,7 +52,7 @@ __device__ __forceinline__ void qk_tok(const bf16* __restrict__ qkv, int qkv_str
                                        const bf16* __restrict__ q_w, const bf16* __restrict__ k_w,
                                        int T, int Hq, int Hkv, int BS, float eps, int apply_rope,
                                        int q_rows) {
-  constexpr int D = 128, HALF = 64, HB = 8;
+  constexpr int D = kKvD, HALF = 64, HB = 8;
   const int t = blockIdx.x * 16 + (threadIdx.x >> 4);
   const int li = threadIdx.x & 15;
   // every lane of a 16-lane row shares the token, so rows exit together (DPP stays valid)
@@ -122,20 +121,12 @@ __device__ __forceinline__ void qk_tok(const bf16* __restrict__ qkv, int qkv_str
       if (is_q) {
         *reinterpret_cast<bf16x8*>(q_out + ((size_t)t * Hq + h) * D + 8 * li) = o;
       } else if (slot >= 0) {
+        // fp8: from the bf16-rounded values (same rounding chain as the bf16 cache + reference)
         const int64_t blk = slot / BS;
         const int off = (int)(slot % BS);
-        const size_t e = ((size_t)blk * Hkv + (h - Hq)) * BS * D + k_swz_offset(off) +
+        const size_t e = AKAP_K_HEAD_BASE(blk, Hkv, h - Hq, BS) + k_token_offset(off) +
                          k_dim_offset(8 * li);
-        if constexpr (F8) {
-          // from the bf16-rounded values (same rounding chain as the bf16 cache + reference)
-          typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-          u32x2 wv;
-          wv[0] = f32x4_to_fp8x4((float)o[0], (float)o[1], (float)o[2], (float)o[3]);
-          wv[1] = f32x4_to_fp8x4((float)o[4], (float)o[5], (float)o[6], (float)o[7]);
-          *reinterpret_cast<u32x2*>(reinterpret_cast<uint8_t*>(k_cache) + e) = wv;
-        } else {
-          *reinterpret_cast<bf16x8*>(reinterpret_cast<bf16*>(k_cache) + e) = o;
-        }
+        st_kv8<F8>(k_cache, e, o);
       }
     }
   }
@@ -164,7 +155,7 @@ __device__ __forceinline__ void v_span(const bf16* __restrict__ qkv, int qkv_str
                                        const int64_t* __restrict__ slots, int T, int Hq, int Hkv,
                                        int BS, int span_id, bf16* __restrict__ v_tail,
                                        const int* __restrict__ tail_slot, int num_decode) {
-  constexpr int D = 128;
+  constexpr int D = kKvD;
   constexpr int NL = (V_ROWS * (D / 8) + 255) / 256;  // row pieces per thread
   __shared__ bf16 tile[V_ROWS][D];
   __shared__ int64_t sl_s[V_ROWS + 1];  // slots[t0 - 1 + i] (-1 outside the batch)
@@ -221,17 +212,17 @@ __device__ __forceinline__ void v_span(const bf16* __restrict__ qkv, int qkv_str
     const int64_t blk = s / BS;
     const int off = (int)(s % BS);
     const int i0 = off & 7;
-    const size_t g = ((size_t)blk * Hkv + vh) * D * BS + (off >> 3) * D * 8 + d * 8;
+    const size_t g = AKAP_V_HEAD_BASE(blk, Hkv, vh, BS) + AKAP_V_GROUP_OFFSET(off) + d * 8;
     // V tail (bf16): this sequence's partial group, token-major; element (token k, dim d)
     const int tsl = (!F8 && v_tail != nullptr) ? tail_slot[t] : -1;
-    bf16* trow = tsl >= 0 ? v_tail + ((size_t)tsl * Hkv + vh) * 8 * D + d : nullptr;
+    bf16* trow = tsl >= 0 ? v_tail + AKAP_V_TAIL_BASE(tsl, Hkv, vh) + d : nullptr;
     if (tsl >= 0 && t < num_decode && i0 + n == 8 && n < 8) {
       // a decode row completing its group: the group's earlier tokens live in the tail (decode
       // steps write no partial V lines) -> the whole [D][8] group, 16 full lines
       bf16x8 v;
 #pragma unroll
       for (int k = 0; k < 8; ++k) v[k] = k < i0 ? trow[(size_t)k * D] : tile[i + k - i0][d];
-      *reinterpret_cast<bf16x8*>(reinterpret_cast<bf16*>(v_cache) + g) = v;
+      st_kv8<false>(v_cache, g, v);
       continue;
     }
     if (tsl >= 0 && i0 + n < 8) {
@@ -243,23 +234,9 @@ __device__ __forceinline__ void v_span(const bf16* __restrict__ qkv, int qkv_str
       bf16x8 v;
 #pragma unroll
       for (int k = 0; k < 8; ++k) v[k] = tile[i + k][d];
-      if constexpr (F8) {
-        typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-        u32x2 w;
-        w[0] = f32x4_to_fp8x4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
-        w[1] = f32x4_to_fp8x4((float)v[4], (float)v[5], (float)v[6], (float)v[7]);
-        *reinterpret_cast<u32x2*>(reinterpret_cast<uint8_t*>(v_cache) + g) = w;
-      } else {
-        *reinterpret_cast<bf16x8*>(reinterpret_cast<bf16*>(v_cache) + g) = v;
-      }
+      st_kv8<F8>(v_cache, g, v);
     } else {
-      for (int k = 0; k < n; ++k) {
-        const size_t e = g + (off & 7) + k;
-        if constexpr (F8)
-          reinterpret_cast<uint8_t*>(v_cache)[e] = f32_to_fp8((float)tile[i + k][d]);
-        else
-          reinterpret_cast<bf16*>(v_cache)[e] = tile[i + k][d];
-      }
+      for (int k = 0; k < n; ++k) st_kv1<F8>(v_cache, g + (off & 7) + k, tile[i + k][d]);
     }
   }
 }
@@ -272,7 +249,6 @@ __device__ __forceinline__ void v_item(const bf16* __restrict__ qkv, int qkv_str
                                        void* __restrict__ v_cache,
                                        const int64_t* __restrict__ slots, int T, int Hq, int Hkv,
                                        int BS, int vblk) {
-  constexpr int D = 128;
   const int item = (vblk * 256 + threadIdx.x) >> 4;
   const int li = threadIdx.x & 15;
   if (item >= T * Hkv) return;
@@ -280,16 +256,13 @@ __device__ __forceinline__ void v_item(const bf16* __restrict__ qkv, int qkv_str
   const int64_t slot = slots[t];
   if (slot < 0) return;
   const bf16x8 v = *reinterpret_cast<const bf16x8*>(qkv + (size_t)t * qkv_stride +
-                                                    (Hq + Hkv + vh) * D + 8 * li);
+                                                    (Hq + Hkv + vh) * kKvD + 8 * li);
   const int64_t blk = slot / BS;
   const int off = (int)(slot % BS);
-  const size_t e = ((size_t)blk * Hkv + vh) * D * BS + (off >> 3) * D * 8 + (off & 7) +
+  const size_t e = AKAP_V_HEAD_BASE(blk, Hkv, vh, BS) + AKAP_V_GROUP_OFFSET(off) + (off & 7) +
                    (size_t)(8 * li) * 8;
 #pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    if constexpr (F8) reinterpret_cast<uint8_t*>(v_cache)[e + 8 * k] = f32_to_fp8((float)v[k]);
-    else reinterpret_cast<bf16*>(v_cache)[e + 8 * k] = v[k];
-  }
+  for (int k = 0; k < 8; ++k) st_kv1<F8>(v_cache, e + 8 * k, v[k]);
 }
 
 template <bool F8>
@@ -344,25 +317,12 @@ __global__ __launch_bounds__(256) void reshape_and_cache_kernel(
   const int t = item / Hkv, h = item % Hkv;
   const int64_t slot = slots[t];
   if (slot < 0) return;
-  const int64_t blk = slot / BS;
-  const int off = (int)(slot % BS);
   bf16x8 kv = *reinterpret_cast<const bf16x8*>(k + ((size_t)t * Hkv + h) * D + 8 * li);
   bf16x8 vv = *reinterpret_cast<const bf16x8*>(v + ((size_t)t * Hkv + h) * D + 8 * li);
-  const size_t ke = ((size_t)blk * Hkv + h) * BS * D + k_swz_offset(off) + k_dim_offset(8 * li);
-  const size_t ve = ((size_t)blk * Hkv + h) * D * BS + (off >> 3) * D * 8 + (off & 7);
-  if constexpr (F8) {
-    uint32_t* kd = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(k_cache) + ke);
-    kd[0] = f32x4_to_fp8x4((float)kv[0], (float)kv[1], (float)kv[2], (float)kv[3]);
-    kd[1] = f32x4_to_fp8x4((float)kv[4], (float)kv[5], (float)kv[6], (float)kv[7]);
-    uint8_t* vd = reinterpret_cast<uint8_t*>(v_cache) + ve;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) vd[(size_t)(8 * li + j) * 8] = f32_to_fp8((float)vv[j]);
-  } else {
-    *reinterpret_cast<bf16x8*>(reinterpret_cast<bf16*>(k_cache) + ke) = kv;
-    bf16* vd = reinterpret_cast<bf16*>(v_cache) + ve;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) vd[(size_t)(8 * li + j) * 8] = vv[j];
-  }
+  const int64_t blk = slot / BS;
+  const int off = (int)(slot % BS);
+  kv_store_k<F8>(k_cache, Hkv, BS, h, blk, off, li, kv);
+  kv_store_v_token<F8>(v_cache, Hkv, BS, h, blk, off, li, vv);
 }
 
 void launch_reshape_and_cache(const void* k, const void* v, void* k_cache, void* v_cache,

@@ -26,7 +26,7 @@
 namespace {
 
 using at::Tensor;
-using akap::OpArgs, akap::kAlign16, akap::kContig, akap::kLastContig;
+using akap::OpArgs, akap::kAlign16, akap::kContig, akap::kLastContig, akap::kKvD;
 
 hipStream_t cur_stream() { return c10::hip::getCurrentHIPStream().stream(); }
 
@@ -59,24 +59,24 @@ void fused_add_rmsnorm(Tensor out, Tensor residual, Tensor x, Tensor w, double e
                                  out.dim() > 1 ? out.stride(-2) : d, (float)eps, cur_stream());
 }
 
-// The paged KV cache of one layer: K [NB, Hkv, BS, 128] and V [NB, Hkv, BS/8, 128, 8] (8-token
-// groups), both contiguous and both bf16, or both uint8 holding OCP e4m3fn bytes
-// (--kv-cache-dtype fp8); BS a multiple of 32 (K cache chunk layout).
+// The paged KV cache of one layer (layout: host_contract.h): K [NB, Hkv, BS, 128] and
+// V [NB, Hkv, BS/8, 128, 8] (8-token groups), both contiguous and both bf16, or both uint8
+// holding OCP e4m3fn bytes (--kv-cache-dtype fp8); BS a multiple of 32 (K cache chunk layout).
 struct KVCache { int fp8, Hkv, BS; void *k, *v; };
 KVCache kv_cache_of(const OpArgs& a, const Tensor& k_cache, const Tensor& v_cache) {
   KVCache c{};
   c.k = a.ptr(k_cache, "k_cache", {at::kBFloat16, at::kByte});
   c.v = a.ptr(v_cache, "v_cache", {k_cache.scalar_type()});
-  TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(3) == 128, a.op(),
+  TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(3) == kKvD, a.op(),
               ": k_cache must be [NB,Hkv,BS,128] (head_dim 128)");
   c.fp8 = k_cache.scalar_type() == at::kByte;
   c.Hkv = k_cache.size(1);
   c.BS = k_cache.size(2);
-  TORCH_CHECK(c.BS % 32 == 0, a.op(),
+  TORCH_CHECK(c.BS % akap::kKvChunk == 0, a.op(),
               ": k_cache block size must be a multiple of 32 (K cache chunk layout)");
   TORCH_CHECK(v_cache.dim() == 5 && v_cache.size(0) == k_cache.size(0) &&
-                  v_cache.size(1) == c.Hkv && v_cache.size(2) * 8 == c.BS &&
-                  v_cache.size(3) == 128 && v_cache.size(4) == 8,
+                  v_cache.size(1) == c.Hkv && v_cache.size(2) * akap::kKvGroup == c.BS &&
+                  v_cache.size(3) == kKvD && v_cache.size(4) == akap::kKvGroup,
               a.op(), ": v_cache must be [NB,Hkv,BS/8,128,8] beside k_cache [NB,Hkv,BS,128]");
   return c;
 }
@@ -90,8 +90,8 @@ VTail v_tail_of(const OpArgs& a, const KVCache& kv, const std::optional<Tensor>&
   TORCH_CHECK(!kv.fp8, a.op(), ": v_tail needs a bf16 KV cache");
   TORCH_CHECK(tail_slot.has_value(), a.op(), ": tail_slot must come with v_tail");
   VTail t{a.bf16(*v_tail, "v_tail"), a.ptr<int>(*tail_slot, "tail_slot", rows)};
-  TORCH_CHECK(v_tail->dim() == 4 && v_tail->size(1) == kv.Hkv && v_tail->size(2) == 8 &&
-                  v_tail->size(3) == 128,
+  TORCH_CHECK(v_tail->dim() == 4 && v_tail->size(1) == kv.Hkv &&
+                  v_tail->size(2) == akap::kVTailRows && v_tail->size(3) == kKvD,
               a.op(), ": v_tail must be contiguous bf16 [slots, Hkv, 8, 128]");
   return t;
 }
@@ -108,7 +108,7 @@ void qk_norm_rope_cache(Tensor qkv, Tensor q_out, Tensor k_cache, Tensor v_cache
               ": qkv must be 2-D and Hkv the cache's");
   const int T = qkv.size(0);
   TORCH_CHECK(q_rows >= -1 && q_rows <= T, a.op(), ": q_rows out of range");
-  TORCH_CHECK(qkv.size(1) >= (Hq + 2 * Hkv) * 128, a.op(), ": qkv too narrow");
+  TORCH_CHECK(qkv.size(1) >= (Hq + 2 * Hkv) * kKvD, a.op(), ": qkv too narrow");
   TORCH_CHECK(!v_tail || !decode, a.op(),
               ": v_tail is written by the span (prefill / mixed) role only");
   TORCH_CHECK(!v_tail || (num_decode >= 0 && num_decode <= T), a.op(),
@@ -116,10 +116,10 @@ void qk_norm_rope_cache(Tensor qkv, Tensor q_out, Tensor k_cache, Tensor v_cache
   const VTail vt = v_tail_of(a, kv, v_tail, tail_slot, T);
   akap::launch_qk_norm_rope_cache(
       a.bf16(qkv, "qkv", 0, kLastContig), qkv.stride(0),
-      a.bf16(q_out, "q_out", (q_rows < 0 ? T : q_rows) * Hq * 128), kv.k, kv.v,
+      a.bf16(q_out, "q_out", (q_rows < 0 ? T : q_rows) * Hq * kKvD), kv.k, kv.v,
       a.ptr<int64_t>(positions, "positions", T), a.ptr<int64_t>(slots, "slots", T),
-      a.ptr<float>(cos_sin, "cos_sin", apply_rope ? 128 : 0), a.bf16(q_w, "q_w", 128),
-      a.bf16(k_w, "k_w", 128), T, Hq, Hkv, 128, kv.BS, (float)eps, apply_rope ? 1 : 0,
+      a.ptr<float>(cos_sin, "cos_sin", apply_rope ? kKvD : 0), a.bf16(q_w, "q_w", kKvD),
+      a.bf16(k_w, "k_w", kKvD), T, Hq, Hkv, kKvD, kv.BS, (float)eps, apply_rope ? 1 : 0,
       cur_stream(), kv.fp8, decode ? 1 : 0, vt.v_tail, vt.tail_slot, (int)num_decode,
       (int)q_rows);
 }
@@ -127,11 +127,11 @@ void qk_norm_rope_cache(Tensor qkv, Tensor q_out, Tensor k_cache, Tensor v_cache
 void reshape_and_cache(Tensor k, Tensor v, Tensor k_cache, Tensor v_cache, Tensor slots) {
   const OpArgs a = on_gpu("reshape_and_cache", k, "k");
   const KVCache kv = kv_cache_of(a, k_cache, v_cache);
-  TORCH_CHECK(k.dim() == 3 && k.size(1) == kv.Hkv && k.size(2) == 128, a.op(),
+  TORCH_CHECK(k.dim() == 3 && k.size(1) == kv.Hkv && k.size(2) == kKvD, a.op(),
               ": k must be [T, Hkv, 128] with the cache's Hkv");
   const int T = k.size(0);
   akap::launch_reshape_and_cache(a.bf16(k, "k"), a.bf16(v, "v", k.numel()), kv.k, kv.v,
-                                 a.ptr<int64_t>(slots, "slots", T), T, kv.Hkv, 128, kv.BS,
+                                 a.ptr<int64_t>(slots, "slots", T), T, kv.Hkv, kKvD, kv.BS,
                                  cur_stream(), kv.fp8);
 }
 
@@ -150,7 +150,7 @@ void silu_and_mul(Tensor out, Tensor x) {
 akap::AttnParams attn_params(const OpArgs& a, const KVCache& kv, Tensor& out, Tensor& q,
                              Tensor& block_tables, Tensor& seq_lens, int64_t rows, int64_t G,
                              double scale) {
-  TORCH_CHECK(q.dim() == 3 && q.size(2) == 128, a.op(), ": q / out must be [T, Hq, 128]");
+  TORCH_CHECK(q.dim() == 3 && q.size(2) == kKvD, a.op(), ": q / out must be [T, Hq, 128]");
   const int B = seq_lens.numel();
   akap::AttnParams p{};
   p.Hq = q.size(1);
@@ -158,7 +158,7 @@ akap::AttnParams attn_params(const OpArgs& a, const KVCache& kv, Tensor& out, Te
   p.G = G;
   p.BS = kv.BS;
   TORCH_CHECK(p.Hq == p.Hkv * G, a.op(), ": Hq must equal Hkv * G");
-  p.q = (const __bf16*)a.bf16(q, "q", rows * p.Hq * 128);
+  p.q = (const __bf16*)a.bf16(q, "q", rows * p.Hq * kKvD);
   p.out = (__bf16*)a.bf16(out, "out", q.numel());
   p.kv_fp8 = kv.fp8;
   p.k_cache = kv.k;
@@ -198,12 +198,12 @@ void set_raw_qkv(const OpArgs& a, akap::AttnParams& p, const Tensor& qkv, int64_
                  const std::optional<Tensor>& q_w, const std::optional<Tensor>& k_w,
                  double eps) {
   TORCH_CHECK(qkv.dim() == 2 && qkv.size(0) >= rows &&
-                  qkv.size(1) >= (p.Hq + 2 * p.Hkv) * 128,
+                  qkv.size(1) >= (p.Hq + 2 * p.Hkv) * kKvD,
               a.op(), ": qkv must be [rows, >= (Hq + 2 Hkv) * 128]");
   TORCH_CHECK(qkv.stride(0) % 8 == 0, a.op(), ": qkv rows must be 16-byte aligned");
-  TORCH_CHECK(cos_sin.dim() == 2 && cos_sin.size(1) == 128, a.op(),
+  TORCH_CHECK(cos_sin.dim() == 2 && cos_sin.size(1) == kKvD, a.op(),
               ": cos_sin must be contiguous fp32 [max_pos, 128]");
-  TORCH_CHECK((!q_w || q_w->numel() == 128) && (!k_w || k_w->numel() == 128), a.op(),
+  TORCH_CHECK((!q_w || q_w->numel() == kKvD) && (!k_w || k_w->numel() == kKvD), a.op(),
               ": q_w / k_w must be contiguous bf16 [128]");
   p.q = nullptr;
   p.qkv = (const __bf16*)a.bf16(qkv, "qkv", 0, kLastContig | kAlign16);
@@ -228,7 +228,7 @@ void set_split_kv(const OpArgs& a, akap::AttnParams& p, const Tensor& part_m,
   const int64_t n = (int64_t)B * p.Hkv * num_parts * p.G;
   p.part_m = a.ptr<float>(part_m, "part_m", n);
   p.part_l = a.ptr<float>(part_l, "part_l", n);
-  p.part_o = a.ptr<float>(part_o, "part_o", n * 128);
+  p.part_o = a.ptr<float>(part_o, "part_o", n * kKvD);
 }
 
 void paged_attention_prefill(Tensor out, Tensor q, Tensor k_cache, Tensor v_cache,
@@ -425,11 +425,12 @@ static akap::KvWriteArgs kv_write_args(const OpArgs& o, const std::vector<Tensor
   const VTail vt = v_tail_of(o, kv, t[7], t[8], B);
   TORCH_CHECK(!kv.fp8 && t[7].size(0) >= 1, o.op(), ": kv_write needs a bf16 KV cache");
   TORCH_CHECK(Hq > 0 && qkv.dim() == 2 && qkv.size(0) >= B &&
-                  qkv.size(1) >= (Hq + 2 * kv.Hkv) * 128 && qkv.stride(0) % 8 == 0,
+                  qkv.size(1) >= (Hq + 2 * kv.Hkv) * kKvD && qkv.stride(0) % 8 == 0,
               o.op(), ": kv_write qkv must be [>= B, >= (Hq + 2 Hkv) * 128] in 16-byte rows");
-  TORCH_CHECK(cos_sin.dim() == 2 && cos_sin.size(1) == 128, o.op(),
+  TORCH_CHECK(cos_sin.dim() == 2 && cos_sin.size(1) == kKvD, o.op(),
               ": kv_write cos_sin must be contiguous fp32 [max_pos, 128]");
-  TORCH_CHECK(k_w.numel() == 0 || k_w.numel() == 128, o.op(), ": kv_write k_w must be bf16 [128]");
+  TORCH_CHECK(k_w.numel() == 0 || k_w.numel() == kKvD, o.op(),
+              ": kv_write k_w must be bf16 [128]");
   const int room = pro == akap::PRO_PLAIN
                        ? akap::kv_rider_blocks(M, N, epi, splitk, bn, ns, bm, cus, B, kv.Hkv, true,
                                                1, true, false)
@@ -441,7 +442,7 @@ static akap::KvWriteArgs kv_write_args(const OpArgs& o, const std::vector<Tensor
   k.positions = o.ptr<int64_t>(positions, "kv_write positions", B);
   k.slots = o.ptr<int64_t>(slots, "kv_write slots", B);
   k.cos_sin = o.ptr<float>(cos_sin, "kv_write cos_sin");
-  k.k_w = k_w.numel() ? o.bf16(k_w, "kv_write k_w", 128) : nullptr;
+  k.k_w = k_w.numel() ? o.bf16(k_w, "kv_write k_w", kKvD) : nullptr;
   k.eps = (float)eps;
   k.k_cache = kv.k;
   k.v_cache = kv.v;

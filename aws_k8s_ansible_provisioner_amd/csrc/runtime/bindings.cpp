@@ -96,6 +96,18 @@ static void bind_contract(py::module_ m) {
     const DGemmContract c = dgemm_contract(M, N, K, pro, epi, splitk, pf, bn, ns, bm, inlaunch, cus);
     return py::make_tuple(c.supported, c.family, c.inlaunch, c.ws_floats, c.ticket_ints);
   });
+  // the paged KV cache layout (element offsets)
+  m.attr("KV_HEAD_DIM") = kKvD;
+  m.attr("KV_GROUP") = kKvGroup;
+  m.attr("KV_CHUNK") = kKvChunk;
+  m.attr("V_TAIL_ROWS") = kVTailRows;
+  m.def("k_head_base", &k_head_base);
+  m.def("v_head_base", &v_head_base);
+  m.def("k_token_offset", &k_token_offset);
+  m.def("k_dim_offset", &k_dim_offset);
+  m.def("v_group_offset", &v_group_offset);
+  m.def("v_elem_offset", &v_elem_offset);
+  m.def("v_tail_row_offset", &v_tail_row_offset);
   m.attr("KV_RIDER_ROWS") = kKvRiderRows;
   m.def("dgemm_wgs_per_cu", &dgemm_wgs_per_cu);
   m.def("kv_rider_blocks", &kv_rider_blocks);

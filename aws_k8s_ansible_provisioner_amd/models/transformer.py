@@ -573,7 +573,7 @@ class DecoderLM:
         for seg in segs:
             NB = seg.shape[2]
             ks += [seg[l, 0].view(NB, self.hkv, block_size, self.D) for l in range(seg.shape[0])]
-            vs += [seg[l, 1].view(NB, self.hkv, block_size // 8, self.D, 8)
+            vs += [seg[l, 1].view(NB, self.hkv, block_size // ops.KV_GROUP, self.D, ops.KV_GROUP)
                    for l in range(seg.shape[0])]
         return ks, vs
 

@@ -7,7 +7,8 @@ Every op dispatches on the device of its inputs:
   * CPU tensors  -> a plain PyTorch reference of the same op (used by the CPU test
     suite, the CPU mock engine and as the numerics oracle of the GPU tests).
 
-Layouts shared with the kernels (see csrc/kernels/rope_cache.hip):
+Layouts shared with the kernels (defined once, in csrc/kernels/host_contract.h, "paged KV
+cache layout"; `_runtime.contract` exposes its constants and offset functions):
   K cache [num_blocks, Hkv, BS, D], V cache [num_blocks, Hkv, BS/8, D, 8] (8-token groups).
 """
 from __future__ import annotations
@@ -78,7 +79,9 @@ def native_available() -> bool:
 # The kernels' host-side contract (csrc/kernels/host_contract.h) is read through _contract():
 # the CPU-built _runtime module, loaded on first use.  These module attributes are its constants.
 _CONTRACT_CONSTANTS = ("CTR_STRIDE", "GEMM_CTR_INTS", "GEMM_CTR_ERR", "DECODE_MAX_PART",
-                       "SAMPLE_MAX_CHUNKS", "SAMPLE_WS_PER_ROW")
+                       "SAMPLE_MAX_CHUNKS", "SAMPLE_WS_PER_ROW",
+                       # the paged KV cache layout: head dim, V group / K chunk tokens, tail rows
+                       "KV_HEAD_DIM", "KV_GROUP", "KV_CHUNK", "V_TAIL_ROWS")
 
 
 def __getattr__(name: str):
@@ -277,7 +280,8 @@ def decode_workspace(max_seqs: int, num_kv_heads: int, gqa_group: int, num_parts
     n = max(1, max_seqs * num_kv_heads * max(num_parts, 1) * gqa_group)
     pm = torch.empty(n, dtype=torch.float32, device=device)
     pl = torch.empty(n, dtype=torch.float32, device=device)
-    po = torch.empty(n * 128 if num_parts > 1 else 1, dtype=torch.float32, device=device)
+    po = torch.empty(n * _contract().KV_HEAD_DIM if num_parts > 1 else 1, dtype=torch.float32,
+                     device=device)
     return pm, pl, po
 
 
@@ -478,8 +482,9 @@ def dgemm(x: torch.Tensor, w: torch.Tensor, pro: int = PRO_PLAIN, splitk: int = 
         if kv_write is not None:  # the reference writer (its cache is always complete: no tail)
             kw = kv_write
             nb = kw.positions.numel()
-            ref.qk_norm_rope_cache(kw.qkv[:nb], torch.empty(nb, kw.num_q_heads, 128,
-                                                            dtype=kw.qkv.dtype),
+            ref.qk_norm_rope_cache(kw.qkv[:nb],
+                                   torch.empty(nb, kw.num_q_heads, _contract().KV_HEAD_DIM,
+                                               dtype=kw.qkv.dtype),
                                    kw.k_cache, kw.v_cache, kw.positions, kw.slots, kw.cos_sin,
                                    None, kw.k_w, kw.num_q_heads, kw.k_cache.shape[1], kw.eps, True)
         if pro == PRO_ADDNORM:

@@ -4,8 +4,11 @@ They define the semantics the HIP kernels are tested against and serve the CPU
 engine path.  Cache layouts (BS % 32 == 0, D = 128 on the GPU path):
   K [NB, Hkv, BS, D] shape, stored MFMA-fragment ordered inside each 32-token chunk:
     [BS/32][tile tt 2][k-step D/32][row r 16][32 dims], chunk token o = 8*(r>>2)+4*tt+(r&3)
-    (csrc/kernels/common.h k_swz_offset) -- use k_tokens()/write_k() to index it;
+    -- use k_tokens()/write_k() to index it;
   V [NB, Hkv, BS/8, D, 8] (8-token groups, dim-major).
+The kernels' definition is csrc/kernels/host_contract.h ("paged KV cache layout"); this module
+derives the layout on its own (views and permutes, no offset arithmetic shared with that header)
+and tests/test_kv_layout_cpu.py checks the two against each other.
 """
 from __future__ import annotations
 

@@ -19,7 +19,7 @@ from aws_k8s_ansible_provisioner_amd.ops.gemm_variant import Variant
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-D, BS = 128, 32
+D = 128
 STEPS_ROOM = 12  # cache blocks cover this many tokens past a sequence's first new token
 
 # position of the new token per row.  In-group offsets 7 (group flush), 0, 3, 6; block offsets
@@ -41,8 +41,9 @@ GEMM_N = 64
 class Case:
     """One decode batch: random pre-filled caches and tail, a block table, the new tokens."""
 
-    def __init__(self, positions, hq, hkv, seed, dead=()):
+    def __init__(self, positions, hq, hkv, seed, dead=(), BS=32):
         g = torch.Generator().manual_seed(seed)
+        self.BS = BS
         B = len(positions)
         self.B, self.hq, self.hkv, self.G = B, hq, hkv, hq // hkv
         nblk = [(p + STEPS_ROOM) // BS + 1 for p in positions]
@@ -70,7 +71,7 @@ class Case:
         self.btg = self.bt.to(DEV)
 
     def step_inputs(self):
-        B = self.B
+        B, BS = self.B, self.BS
         pos = torch.tensor(self.cur, dtype=torch.int64)
         slots = torch.tensor([int(self.bt[s, self.cur[s] // BS]) * BS + self.cur[s] % BS
                               for s in range(B)], dtype=torch.int64)
@@ -131,13 +132,13 @@ def _device_caches(c):
 @pytest.mark.parametrize("name,variant,K", GEMMS, ids=[g[0] for g in GEMMS])
 @pytest.mark.parametrize("heads", [(16, 8), (32, 8), (8, 4)], ids=["16/8", "32/8", "8/4"])
 @pytest.mark.parametrize("B", [1, 5, 19])
-def test_rider_writes_the_bytes_attention_writes(B, heads, name, variant, K):
+def test_rider_writes_the_bytes_attention_writes(B, heads, name, variant, K, BS=32):
     """B = 19 with 8/4 heads: 19 * 4 pairs is no multiple of the 8 pairs of a rider pass.  Rows
     1 and 2 (B >= 5) are a slot = -1 row and a tail_slot = -1 row."""
     hq, hkv = heads
     assert ops.kv_rider_blocks(B, GEMM_N, variant, B, hkv) > 0
     dead = {1: "slot", 2: "tail"} if B >= 5 else {}
-    c = Case(POSITIONS[:B], hq, hkv, seed=100 * B + hq, dead=dead)
+    c = Case(POSITIONS[:B], hq, hkv, seed=100 * B + hq, dead=dead, BS=BS)
     x, w = _gemm_operands(B, K, seed=B + K)
     A, Bc = _device_caches(c), _device_caches(c)
     before = tuple(t.clone() for t in A)
@@ -146,6 +147,24 @@ def test_rider_writes_the_bytes_attention_writes(B, heads, name, variant, K):
     if B >= 5:
         assert not torch.equal(Bc[1], before[1])  # row 0 completes a V group
         assert not torch.equal(Bc[2], before[2])
+
+
+# The same at cache block size 64: the K layout's chunk term, zero for every slot at 32, is
+# non-zero for the POSITIONS with p % 64 >= 32 (45, 100, 63, 95, 33), in blocks never block 0.
+@pytest.mark.parametrize("name,variant,K", GEMMS, ids=[g[0] for g in GEMMS])
+@pytest.mark.parametrize("B", [5, 19])
+def test_rider_writes_the_bytes_attention_writes_bs64(B, name, variant, K):
+    test_rider_writes_the_bytes_attention_writes(B, (16, 8) if B == 5 else (8, 4), name, variant,
+                                                 K, BS=64)
+
+
+@pytest.mark.parametrize("name,variant,K", [GEMMS[0], GEMMS[2]], ids=[GEMMS[0][0], GEMMS[2][0]])
+def test_ten_consecutive_steps_bs64(name, variant, K):
+    test_ten_consecutive_steps(name, variant, K, BS=64)
+
+
+def test_one_rider_loops_over_every_row_bs64():
+    test_one_rider_loops_over_every_row(BS=64)
 
 
 def test_dead_rows_leave_every_byte_untouched():
@@ -165,11 +184,11 @@ def test_dead_rows_leave_every_byte_untouched():
 
 
 @pytest.mark.parametrize("name,variant,K", [GEMMS[0], GEMMS[2]], ids=[GEMMS[0][0], GEMMS[2][0]])
-def test_ten_consecutive_steps(name, variant, K):
+def test_ten_consecutive_steps(name, variant, K, BS=32):
     """Groups complete and restart; a slot = -1 row stays dead throughout.  Compared after
     every step."""
-    positions = [1, 5, 8, 13, 31, 200, 30, 26]
-    c = Case(positions, 16, 8, seed=11, dead={3: "slot"})
+    positions = [1, 5, 8, 13, 31, 200, 30, 26] + ([58] if BS == 64 else [])
+    c = Case(positions, 16, 8, seed=11, dead={3: "slot"}, BS=BS)
     x, w = _gemm_operands(len(positions), K, seed=2)
     A, Bc = _device_caches(c), _device_caches(c)
     for _ in range(10):
@@ -177,9 +196,9 @@ def test_ten_consecutive_steps(name, variant, K):
         c.cur = [p + 1 for p in c.cur]
 
 
-def test_one_rider_loops_over_every_row():
+def test_one_rider_loops_over_every_row(BS=32):
     """n_blocks forced to 1: the single rider walks all 19 * 8 * 2 rows."""
-    c = Case(POSITIONS, 16, 8, seed=21, dead={1: "slot", 2: "tail"})
+    c = Case(POSITIONS, 16, 8, seed=21, dead={1: "slot", 2: "tail"}, BS=BS)
     x, w = _gemm_operands(19, 64, seed=4)
     A, Bc = _device_caches(c), _device_caches(c)
     _both_arms(c, A, Bc, Variant(bn=128, ns=6), x, w, blocks=1)

@@ -64,16 +64,17 @@ def _rand_cache(nb, hkv, bs, d=128, seed=0):
 @pytest.mark.parametrize("qk_norm", [True, False])
 @pytest.mark.parametrize("hq,hkv", [(16, 8), (32, 8)])
 @pytest.mark.parametrize("layout", ["random", "prefill"])
-def test_qk_norm_rope_cache(qk_norm, hq, hkv, layout):
+def test_qk_norm_rope_cache(qk_norm, hq, hkv, layout, BS=32):
     torch.manual_seed(2)
-    T, D, BS, NB = 45, 128, 32, 16
+    T, D, NB = 45, 128, 16
     qkv = torch.randn(T, (hq + 2 * hkv) * D, dtype=torch.bfloat16)
     pos = torch.randint(0, 4000, (T,), dtype=torch.int64)
     if layout == "random":
         slots = torch.randperm(NB * BS)[:T].to(torch.int64)
     else:  # two sequences' prefill chunks: complete 8-token V groups + ragged edges
-        slots = torch.cat([torch.arange(3 * BS + 5, 3 * BS + 5 + 30),
-                           torch.arange(9 * BS + 16, 9 * BS + 16 + 15)]).to(torch.int64)
+        # (the runs end 3 tokens into block 4 and 1 token before the end of block 9)
+        slots = torch.cat([torch.arange(4 * BS - 27, 4 * BS - 27 + 30),
+                           torch.arange(10 * BS - 16, 10 * BS - 16 + 15)]).to(torch.int64)
     slots[3] = -1
     cs = ref.rope_cos_sin(4096, D, 1e6)
     qw = torch.randn(D).bfloat16() if qk_norm else None
@@ -91,6 +92,35 @@ def test_qk_norm_rope_cache(qk_norm, hq, hkv, layout):
     _close(q_out, q_ref, atol=3e-2, rtol=2e-2)
     _close(kg, kc2, atol=3e-2, rtol=2e-2)
     _close(vg, vc2, atol=0)
+
+
+# Cache writers at BS = 64: slots in the second 32-token K chunk of blocks other than block 0
+# (at BS = 32 the chunk term of the K layout is zero for every slot).
+@pytest.mark.parametrize("layout", ["random", "prefill"])
+def test_qk_norm_rope_cache_bs64(layout):
+    test_qk_norm_rope_cache(True, 16, 8, layout, BS=64)
+
+
+@pytest.mark.parametrize("fp8", [False, True], ids=["bf16", "fp8"])
+@pytest.mark.parametrize("BS", [32, 64])
+def test_reshape_and_cache(BS, fp8):
+    """A plain scatter of final rows: bf16 is a copy and fp8 one clamp + round-to-nearest-even of
+    a bf16 value on both sides, so the caches are equal byte for byte; a slot of -1 writes
+    nothing, and every byte no slot names stays as it was."""
+    g = torch.Generator().manual_seed(17 + BS)
+    T, hkv, D, NB = 61, 8, 128, 12
+    k = torch.randn(T, hkv, D, generator=g).bfloat16()
+    v = torch.randn(T, hkv, D, generator=g).bfloat16()
+    slots = (torch.randperm((NB - 1) * BS, generator=g)[:T] + BS).to(torch.int64)  # not block 0
+    slots[5] = -1
+    kc, vc = _rand_cache(NB, hkv, BS, D, seed=3)
+    if fp8:
+        kc, vc = _to_fp8_cache(kc, vc)
+    kg, vg = kc.to(DEV), vc.to(DEV)
+    ref.write_cache(k, v, kc, vc, slots)
+    ops.reshape_and_cache(k.to(DEV), v.to(DEV), kg, vg, slots.to(DEV))
+    assert torch.equal(kg.cpu().view(torch.uint8), kc.view(torch.uint8))
+    assert torch.equal(vg.cpu().view(torch.uint8), vc.view(torch.uint8))
 
 
 def _setup_attn(seqs, hq, hkv, bs, seed=0):
@@ -202,16 +232,16 @@ def test_paged_attention_decode(num_parts, part_size, hq, hkv):
 @pytest.mark.parametrize("hq,hkv", [(16, 8), (32, 8), (64, 8)])
 @pytest.mark.parametrize("qk_norm", [True, False])
 @pytest.mark.parametrize("num_parts,part_size", [(1, 4096), (3, 512)])
-def test_paged_attention_decode_fused(hq, hkv, qk_norm, num_parts, part_size, lens=None):
+def test_paged_attention_decode_fused(hq, hkv, qk_norm, num_parts, part_size, lens=None, BS=32):
     """Fused q/k-norm + RoPE + KV write + decode attention vs the reference pipeline."""
     lens = lens or [1, 31, 32, 33, 200, 777, 1500]
     seqs = [(kv, 1) for kv in lens]
-    _, kc, vc, bt, sl, qs = _setup_attn(seqs, hq, hkv, 32, seed=hq + num_parts)
+    _, kc, vc, bt, sl, qs = _setup_attn(seqs, hq, hkv, BS, seed=hq + num_parts)
     B, D = len(lens), 128
     g = torch.Generator().manual_seed(11)
     qkv = torch.randn(B, (hq + 2 * hkv) * D, generator=g).bfloat16()
     pos = (sl - 1).to(torch.int64)
-    slots = torch.tensor([int(bt[s, int(pos[s]) // 32]) * 32 + int(pos[s]) % 32
+    slots = torch.tensor([int(bt[s, int(pos[s]) // BS]) * BS + int(pos[s]) % BS
                           for s in range(B)], dtype=torch.int64)
     slots[2] = -1  # padding row: no cache write
     cs = ref.rope_cos_sin(max(4096, max(lens)), D, 1e6)
@@ -234,6 +264,13 @@ def test_paged_attention_decode_fused(hq, hkv, qk_norm, num_parts, part_size, le
     _close(out, exp, atol=3e-2, rtol=3e-2)
     _close(kg, kc_ref, atol=3e-2, rtol=2e-2)
     _close(vg, vc_ref, atol=0)
+
+
+@pytest.mark.parametrize("num_parts,part_size", [(1, 4096), (3, 512)])
+def test_paged_attention_decode_fused_bs64(num_parts, part_size):
+    """New tokens at block offsets 32, 47, 63 (the second K chunk), 55 and 0, 7, 27."""
+    test_paged_attention_decode_fused(16, 8, True, num_parts, part_size,
+                                      lens=[1, 33, 48, 64, 200, 120, 1500], BS=64)
 
 
 def test_decode_attention_large_score_spike():
@@ -769,14 +806,14 @@ def _to_fp8_cache(kc, vc):
 
 @pytest.mark.parametrize("hq,hkv", [(16, 8), (32, 8)])
 @pytest.mark.parametrize("layout", ["random", "prefill"])
-def test_qk_norm_rope_cache_fp8(hq, hkv, layout):
+def test_qk_norm_rope_cache_fp8(hq, hkv, layout, BS=32):
     torch.manual_seed(31)
-    T, D, BS, NB = 45, 128, 32, 16
+    T, D, NB = 45, 128, 16
     qkv = torch.randn(T, (hq + 2 * hkv) * D, dtype=torch.bfloat16)
     pos = torch.randint(0, 4000, (T,), dtype=torch.int64)
     slots = (torch.randperm(NB * BS)[:T] if layout == "random" else
-             torch.cat([torch.arange(3 * BS + 5, 3 * BS + 35), torch.arange(9 * BS + 16,
-                                                                          9 * BS + 31)]))
+             torch.cat([torch.arange(4 * BS - 27, 4 * BS + 3), torch.arange(10 * BS - 16,
+                                                                          10 * BS - 1)]))
     slots = slots.to(torch.int64)
     cs = ref.rope_cos_sin(4096, D, 1e6)
     qw, kw = torch.randn(D).bfloat16(), torch.randn(D).bfloat16()
@@ -794,13 +831,18 @@ def test_qk_norm_rope_cache_fp8(hq, hkv, layout):
     assert torch.equal(vg.cpu(), vc)  # V is exact: bf16 -> e4m3 on both sides
 
 
+@pytest.mark.parametrize("layout", ["random", "prefill"])
+def test_qk_norm_rope_cache_fp8_bs64(layout):
+    test_qk_norm_rope_cache_fp8(16, 8, layout, BS=64)
+
+
 @pytest.mark.parametrize("num_parts,part_size", [(1, 4096), (3, 512)])
 @pytest.mark.parametrize("fused", [False, True])
-def test_paged_attention_decode_fp8(num_parts, part_size, fused):
-    lens = [1, 31, 33, 200, 777, 1500]
+def test_paged_attention_decode_fp8(num_parts, part_size, fused, lens=None, BS=32):
+    lens = lens or [1, 31, 33, 200, 777, 1500]
     seqs = [(kv, 1) for kv in lens]
     hq, hkv = 16, 8
-    q, kc, vc, bt, sl, qs = _setup_attn(seqs, hq, hkv, 32, seed=41)
+    q, kc, vc, bt, sl, qs = _setup_attn(seqs, hq, hkv, BS, seed=41)
     kc8, vc8 = _to_fp8_cache(kc, vc)
     scale = 1 / math.sqrt(128)
     B, G = len(lens), hq // hkv
@@ -816,7 +858,7 @@ def test_paged_attention_decode_fp8(num_parts, part_size, fused):
     g = torch.Generator().manual_seed(5)
     qkv = torch.randn(B, (hq + 2 * hkv) * 128, generator=g).bfloat16()
     pos = (sl - 1).to(torch.int64)
-    slots = torch.tensor([int(bt[s, int(pos[s]) // 32]) * 32 + int(pos[s]) % 32
+    slots = torch.tensor([int(bt[s, int(pos[s]) // BS]) * BS + int(pos[s]) % BS
                           for s in range(B)], dtype=torch.int64)
     slots[1] = -1  # padding row: no cache write, attends what the cache holds
     cs = ref.rope_cos_sin(4096, 128, 1e6)
@@ -833,6 +875,12 @@ def test_paged_attention_decode_fp8(num_parts, part_size, fused):
     dq = lambda t: t.cpu().view(torch.float8_e4m3fn).float()  # noqa: E731
     _close(dq(kg), dq(kr), atol=1e-2, rtol=0.13)
     assert torch.equal(vg.cpu(), vr)  # the new token's V group is stored back whole
+
+
+@pytest.mark.parametrize("num_parts,part_size", [(1, 4096), (3, 512)])
+def test_paged_attention_decode_fp8_fused_bs64(num_parts, part_size):
+    test_paged_attention_decode_fp8(num_parts, part_size, True,
+                                    lens=[1, 31, 33, 48, 64, 120, 1500], BS=64)
 
 
 @pytest.mark.parametrize("tile_rows", [128])
@@ -1119,11 +1167,11 @@ def test_wide_row_gemm_strided_rows_in_graph():
 
 @pytest.mark.parametrize("qk_norm", [True, False])
 @pytest.mark.parametrize("fp8", [False, True])
-def test_qk_norm_rope_cache_decode_mode(qk_norm, fp8):
+def test_qk_norm_rope_cache_decode_mode(qk_norm, fp8, BS=32, NB=40):
     """decode=True (per-token V writes, one token per sequence) writes the same cache as the
     reference; a slot of -1 writes nothing."""
     torch.manual_seed(5)
-    T, hq, hkv, D, BS, NB = 77, 16, 8, 128, 32, 40
+    T, hq, hkv, D = 77, 16, 8, 128
     qkv = torch.randn(T, (hq + 2 * hkv) * D, dtype=torch.bfloat16)
     pos = torch.randint(0, 4000, (T,), dtype=torch.int64)
     slots = torch.randperm(NB * BS)[:T].to(torch.int64)
@@ -1152,6 +1200,11 @@ def test_qk_norm_rope_cache_decode_mode(qk_norm, fp8):
     else:
         _close(kg, kc, atol=3e-2, rtol=2e-2)
         _close(vg, vc, atol=0)
+
+
+@pytest.mark.parametrize("fp8", [False, True])
+def test_qk_norm_rope_cache_decode_mode_bs64(fp8):
+    test_qk_norm_rope_cache_decode_mode(True, fp8, BS=64, NB=16)
 
 
 @pytest.mark.parametrize("km", [16, 32])
@@ -1257,13 +1310,13 @@ def _v_tokens(vc, bt, s, n, bs=32):
 
 
 @pytest.mark.parametrize("num_parts,part_size", [(1, 4096), (3, 512)])
-def test_v_tail_decode_matches_the_plain_cache_path(num_parts, part_size):
+def test_v_tail_decode_matches_the_plain_cache_path(num_parts, part_size, BS=32):
     """V tail (AttnParams.v_tail): decode steps write the new token's V to its sequence's
     tail and whole 8-token groups to the cache; readers take the partial group from the tail.
     Against a twin cache on the plain per-token path, over 20 steps (fused steps, plus mixed
     steps through the writer kernel + the plain decode kernel): bit-identical attention
     outputs, and identical V for every completed group."""
-    hq, hkv, D, BS = 16, 8, 128, 32
+    hq, hkv, D = 16, 8, 128
     lens = [1, 5, 8, 13, 31, 200, 777]
     steps = 20
     seqs = [(kv + steps, 1) for kv in lens]  # blocks for the prompt + every decode token
@@ -1315,8 +1368,13 @@ def test_v_tail_decode_matches_the_plain_cache_path(num_parts, part_size):
     vA_, vB_ = vA.cpu(), vB.cpu()
     for s, n in enumerate(cur):
         full = n & ~7
-        assert torch.equal(_v_tokens(vA_, bt, s, full), _v_tokens(vB_, bt, s, full)), s
+        assert torch.equal(_v_tokens(vA_, bt, s, full, BS), _v_tokens(vB_, bt, s, full, BS)), s
     assert torch.equal(kA, kB)
+
+
+def test_v_tail_decode_matches_the_plain_cache_path_bs64():
+    """The 20 steps of the sequences that start at 13 and 31 run through block offsets 32..51."""
+    test_v_tail_decode_matches_the_plain_cache_path(1, 4096, BS=64)
 
 
 # ----------------------------------------------------------------------------- prefill GEMM
